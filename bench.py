@@ -13,13 +13,25 @@ region starts (the MV-CNN is outside the path).  The timed steps are passes over
 of the scene (what depends on cameras, image range and sharding only: `config.reused_between_
 steps` lists it); no result of a pass is reused -- every step recomputes traversal, plane sweep,
 mapping, the BP iterations and the depth sweep.  The cost of the FIRST pass over a new scene
-(plan construction included) is reported as `first_pass_ms`.
+(plan construction included) is reported as `first_pass_ms` (--full).
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus 8 --steps 5 --warmup 1
 
-Prints ONE JSON line on rank 0.  Extra objects:
+A plain run does what the headline needs and nothing else: it sets the scene up, runs the plan's
+untimed passes and the W warm-up steps, times the K steps and prints ONE JSON line on rank 0
+(metric / value / unit / ms_per_step / higher_is_better / dtype ..., `step_ms`, the whole path's
+algorithmic `path_roofline`).  --dump-outputs DIR then writes what the last timed step computed:
+every reference image's depth map (`depth_<k>.npy`, what the forward_pass generator yields) and
+the [gx][gy][gz] accumulator (`accumulator.npy`; a fixed seeded sample `accumulator_sample.npy`
+where the whole would take the files past 64 MB), float32.  The inputs are seeded: the same
+arguments give the same inputs in every run.
+
+--full adds the first-pass figures (`first_pass_ms`, `cold_process_first_pass_ms`) and these
+objects, each measured outside the timed region:
   roofline     dominant kernel family: algorithmic bytes of its
                launches in the timed region / their hipEvent durations (per launch, on
                the launch stream, via rn_prof_begin/rn_prof_end), vs the 8 TB/s HBM peak;
@@ -37,6 +49,8 @@ Prints ONE JSON line on rank 0.  Extra objects:
                top-level value; "numpy_restatement" = the reference's own NumPy
                implementation of the MRF stages (mrf/mrf_np.py semantics restated in
                oracle/cpu_reference.py, per-ray Python loop, one process)
+  other_configs BASELINE.json configs[3] and the reference's own workloads (N = 1, config2)
+  ranks        N > 1: what every rank saw
 """
 import argparse
 import json
@@ -163,7 +177,7 @@ def live_pmc(config, family, budget_s=180.0):
                                                   "--warmup", "1", "--no-cpu-baseline", "--no-config4",
                                                   "--no-reference-shapes",     # (their sweeps would
                                                   # be averaged into the counters per launch)
-                                                  "--pmc", "off", "--config", config]
+                                                  "--pmc", "off", "--config", config, "--full"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL,
                                stderr=subprocess.DEVNULL, timeout=min(left, 60.0))
             if r.returncode != 0:
@@ -343,6 +357,31 @@ def reference_shapes(torch, steps=5):
     return out
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, maps, fp, rank, H, W):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy, float32.
+    depth_<k>.npy    reference image k's depth map as the forward_pass generator yields it, [H, W]
+                     (N > 1: written by the rank that assembled it; the others got None for it)
+    accumulator.npy  the pass's [gx][gy][gz] accumulator (rank 0: every rank holds the same one);
+                     where it would take the files past DUMP_BYTES, accumulator_sample.npy instead:
+                     its values at a fixed, seeded sample of flat indices, in index order."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, m in enumerate(maps):
+        if m is not None:
+            np.save(os.path.join(out_dir, "depth_%d.npy" % k), np.ascontiguousarray(m, dtype=np.float32))
+    if rank != 0:
+        return
+    acc = fp.accumulator.detach().float().cpu().numpy()
+    room = (DUMP_BYTES - 4 * H * W * len(maps)) // 4
+    if acc.size <= room:
+        np.save(os.path.join(out_dir, "accumulator.npy"), acc)
+        return
+    idx = np.sort(np.random.default_rng(0).choice(acc.size, size=min(room, 1 << 22), replace=False))
+    np.save(os.path.join(out_dir, "accumulator_sample.npy"), acc.ravel()[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,6 +405,12 @@ def main():
                          "rocprofv3 --pmc passes of this script spawned from this run (live; N = 1 "
                          "only, falls back to the table), read from profiles/pmc_traffic.json "
                          "(table), or left out (off)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: first-pass figures, the "
+                         "per-kernel breakdown and roofline, other configurations, the CPU baseline "
+                         "(the options above apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
     t_wall = {"start": time.perf_counter()}
 
@@ -407,10 +452,11 @@ def main():
     images_range = (0, V, 1)
     t_wall["scene"] = time.perf_counter()
 
-    def step():
+    def step(keep=None):
         out = None
         for out in fp.forward_pass(scene, images_range):
-            pass
+            if keep is not None:
+                keep.append(out)
         return out
 
     def fence():
@@ -428,43 +474,50 @@ def main():
     # object, in the now warm process, handed a NEW scene object (new cameras: every per-scene
     # structure is rebuilt; the buffers come back from the allocator's cache) -- what a caller
     # looping over scenes pays per scene.  Feature maps are resident in both, as in the timed steps.
-    fence()
-    t0 = time.perf_counter()
-    step()
-    fence()
-    cold_process_first_pass_ms = (time.perf_counter() - t0) * 1e3
-    step()          # (the plan's second pass builds the scatter's work list: the process is warm now)
-    from raynet_amd.common.scene import Scene
-    from raynet_amd.synthetic import _FeatureOnlyImage, ring_cameras
-    first_passes = []
-    for _ in range(3):      # three scenes in a row, as a caller looping over scenes would: the median
-        scene = Scene([_FeatureOnlyImage(H, W, c) for c in ring_cameras(V, H, W, focal=1.5 * H)],
-                      scene.bbox)
+    # (--full only; a plain run makes the plan's first pass untimed, on the scene it times)
+    if args.full:
         fence()
         t0 = time.perf_counter()
         step()
         fence()
-        first_passes.append((time.perf_counter() - t0) * 1e3)
-    first_pass_ms = sorted(first_passes)[1]
+        cold_process_first_pass_ms = (time.perf_counter() - t0) * 1e3
+        step()          # (the plan's second pass builds the scatter's work list: the process is warm now)
+        from raynet_amd.common.scene import Scene
+        from raynet_amd.synthetic import _FeatureOnlyImage, ring_cameras
+        first_passes = []
+        for _ in range(3):      # three scenes in a row, as a caller looping over scenes would: the median
+            # (the same cameras as make_synthetic_scene's: the timed steps compute the same either way)
+            scene = Scene([_FeatureOnlyImage(H, W, c) for c in ring_cameras(V, H, W, focal=1.5 * H)],
+                          scene.bbox)
+            fence()
+            t0 = time.perf_counter()
+            step()
+            fence()
+            first_passes.append((time.perf_counter() - t0) * 1e3)
+        first_pass_ms = sorted(first_passes)[1]
+    else:
+        step()
     # (the new plan's second and third pass: work list, the scatter's tile shape settles)
     for _ in range(max(2, args.warmup - 3)):
         step()
     ctx = fp._ctx
     # N > 1: every exchange of the breakdown steps (the all-reduce per BP iteration, the depth
     # rows' way to their owners) is bracketed by a pair of events on its stream (fp.trace)
-    if world > 1:
+    if world > 1 and args.full:
         fp.trace = []
-    # Per-kernel breakdown: untimed steps with every launch bracketed by an event pair.  The
+    # Per-kernel breakdown (--full): untimed steps with every launch bracketed by an event pair.  The
     # timed region then brackets the launches of the dominant family only (--events all: every
     # launch, as the breakdown steps do): an event pair costs the stream a few microseconds,
-    # ~20 of them per step are 1 % of a one-GPU step and 5 % of an eight-GPU one.
+    # ~20 of them per step are 1 % of a one-GPU step and 5 % of an eight-GPU one.  A plain run makes
+    # the same number of untimed passes without events: its timed steps start from the same state.
     fence()
     breakdown_steps = max(1, min(3, args.steps))
-    ctx.prof_begin(capacity=64 * V * breakdown_steps + 64)
+    if args.full:
+        ctx.prof_begin(capacity=64 * V * breakdown_steps + 64)
     for _ in range(breakdown_steps):
         step()
     fence()
-    launches_all = ctx.prof_end()
+    launches_all = ctx.prof_end() if args.full else []
     exchange_ms = {}
     if fp.trace is not None:
         open_ev = {}
@@ -510,7 +563,7 @@ def main():
     # the per-launch durations of every family -- the roofline block's too -- are those of the
     # untimed, eager breakdown steps just before it (roofline.duration_source says which).
     graph_mode = bool(fp.captured)
-    if not graph_mode:
+    if not graph_mode and args.full:
         ctx.prof_begin(capacity=64 * V * max(args.steps, 1) + 64, only=only)
     # the interpreter's cyclic garbage collector is a property of the host process, not of the
     # path: a generation-2 collection of a process that has imported torch pauses it for ~40 ms,
@@ -526,20 +579,25 @@ def main():
     # figures, the plan's settling, the breakdown) are untimed as well; these are the contract's W.
     for _ in range(max(0, args.warmup)):
         step()
+    # --dump-outputs: the last timed step's maps are kept (the others are dropped as before)
+    maps = [] if args.dump_outputs else None
     fence()         # (barrier + synchronize on both sides of the K timed steps)
     t0 = time.perf_counter()
     step_ends = []
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(maps if i == args.steps - 1 else None)
         step_ends.append(time.perf_counter())     # (a pass returns when its last map is on the host)
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
     step_ms = [round((b - a) * 1e3, 3) for a, b in zip([t0] + step_ends[:-1], step_ends)]
-    launches = [l for l in launches_all if only is None or l[0] in only] if graph_mode \
-        else ctx.prof_end()
+    launches = [] if not args.full else \
+        [l for l in launches_all if only is None or l[0] in only] if graph_mode else ctx.prof_end()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, maps, fp, rank, H, W)
+        del maps
     ranks_report = None
-    if world > 1:
+    if world > 1 and args.full:
         # what every rank saw: its own wall time for the K steps, its kernel families' sums and
         # its exchanges (breakdown steps, eager), its share of the rays and of the voxel visits
         mine = dict(ms_per_step=elapsed / args.steps * 1e3,
@@ -549,9 +607,6 @@ def main():
                     rows=int(sum(len(fp.ray_index[r]) for r in fp.ray_index)))
         gathered = [None] * world
         dist.all_gather_object(gathered, mine)
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         keys = ("ms_per_step", "exchange_ms_per_step", "gather_ms_per_step", "kernel_ms_per_step")
         ranks_report = {k: [round(g[k], 4) for g in gathered] for k in keys}
         ranks_report["rows"] = [g["rows"] for g in gathered]
@@ -567,6 +622,11 @@ def main():
             "(3 per step) / the depth rows' way to the maps' owners; a rank that arrives early "
             "waits inside them, so they hold the imbalance too.  kernel: sum of the rank's "
             "launches.  rows, voxel_share_over_mean: the shard.")
+    if world > 1:
+        # the line's step time is the slowest rank's
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
 
     rays_per_step = V * H * W
     value = rays_per_step * args.steps / elapsed
@@ -705,12 +765,13 @@ def main():
                for k, v in sorted(fam.items())}
 
     t_wall["counters"] = time.perf_counter()
-    # ---- BASELINE.json configs[3] on the side (N = 1, default run only) ------------------------
+    # ---- BASELINE.json configs[3] on the side (N = 1, --full only) ----------------------------
     # The headline is config 2; config 4 (9 views, 128 planes, 256^3, M = 768) gets ONE figure in
     # the same line so that a driver-run record of it exists: a fresh driver, 5 untimed passes
     # (plan, work list, the scatter's tile shape), 5 timed ones.  Outside the timed region above.
     other_configs = None
-    if world == 1 and args.config == "config2" and args.also_config4 and args.schedule == "resident":
+    if args.full and world == 1 and args.config == "config2" and args.also_config4 and \
+            args.schedule == "resident":
         try:
             c4 = CONFIGS["config4"]
             scene4, bank4 = make_synthetic_scene(H=c4["H"], W=c4["W"], n_views=c4["views"], F=c4["F"],
@@ -747,8 +808,9 @@ def main():
         except Exception as e:              # (never at the cost of the headline)
             other_configs = {"config4": {"error": repr(e)[:200]}}
 
-    # ---- the reference's OWN workloads on the side (N = 1, default run only) -------------------
-    if world == 1 and args.config == "config2" and args.reference_shapes and args.schedule == "resident":
+    # ---- the reference's OWN workloads on the side (N = 1, --full only) -----------------------
+    if args.full and world == 1 and args.config == "config2" and args.reference_shapes and \
+            args.schedule == "resident":
         other_configs = dict(other_configs or {})
         try:
             fp._plan = None
@@ -759,14 +821,14 @@ def main():
             other_configs["reference_shapes"] = {"error": repr(e)[:300]}
 
     t_wall["config4"] = time.perf_counter()
-    # ---- CPU baseline, two legs on bounded ray samples drawn from ALL reference images -------
+    # ---- CPU baseline (--full), two legs on bounded ray samples drawn from ALL reference images
     #  port              the C oracle's fused K1 / K2 (whole path, OpenMP over rays, all cores)
     #  numpy_restatement oracle/cpu_reference.py = the reference's own CPU implementation
     #                    (mrf/mrf_np.py: per-ray Python loop, one process) of the stages it
     #                    has one for -- the 3 BP sweeps + the depth sweep; the plane sweep has
     #                    no NumPy twin in the reference, its inputs come from the port
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_reference, oracle
         threads = oracle.Oracle.max_threads()
         o = oracle.Oracle(M=cfg["M"], D=cfg["D"], N=gp.neighbors + 1, F=cfg["F"], H=H, W=W,
@@ -949,15 +1011,6 @@ def main():
                            "the scatter's settled tile shape; N > 1: the step's captured HIP graph",
                            "NOTHING of a pass's results: traversal, plane sweep, mapping, 3 BP "
                            "iterations, depth sweep and the maps' copies run in every step"]},
-            "first_pass_ms": round(first_pass_ms, 3),
-            "first_pass_ms_all": [round(t, 3) for t in first_passes],
-            "cold_process_first_pass_ms": round(cold_process_first_pass_ms, 3),
-            "first_pass": "first_pass_ms: this driver handed a NEW scene object (every per-scene "
-                          "structure rebuilt, then one pass; three scenes in a row, the median) -- what "
-                          "the reference's one-pass-per-scene caller pays per scene "
-                          "(scripts/forward_pass.py:120-142); cold_process: "
-                          "the process's very first pass (HIP module load, context, first-touch "
-                          "allocation on top).  Both outside the timed region.",
             "ray_sweeps_per_s": round(4 * value, 1),
             # SURVEY.md 8(d)'s whole-path figure: (3 B_bp + B_de) bytes per ray, B_bp = 4NF HfWf/HW
             # + 20 c, B_de = 4NF HfWf/HW + 8 c + 4 (features once per sweep, per traversed voxel:
@@ -966,24 +1019,39 @@ def main():
             "step_ms": dict(each=step_ms[:32], min=min(step_ms), median=sorted(step_ms)[len(step_ms) // 2],
                             what="this rank's wall time of every timed step (ms_per_step is their mean "
                                  "incl. the closing barrier, MAX over ranks)"),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "other_configs": other_configs,
             "wall_s": {"imports_scene": round(t_wall["scene"] - t_wall["start"], 1),
-                       "warmup_breakdown_timed": round(t_wall["timed"] - t_wall["scene"], 1),
-                       "counter_passes": round(t_wall["counters"] - t_wall["timed"], 1),
-                       "config4": round(t_wall["config4"] - t_wall["counters"], 1),
-                       "cpu_baseline": round(time.perf_counter() - t_wall["config4"], 1)},
-            "kernels": kernels,
-            "ranks": ranks_report,
+                       "warmup_timed": round(t_wall["timed"] - t_wall["scene"], 1)},
             "step_capture": {"captured": bool(fp.captured), "extra_warmup_steps": extra_warmup,
                              "timed_region": "graph replays (launch durations: the eager breakdown "
                                              "steps before it)"
-                             if graph_mode else "eager launches bracketed by event pairs"},
-            "kernel_events": {"breakdown_steps_untimed": breakdown_steps,
-                              "timed_region": "all launches" if only is None else
-                              "launches of %s only" % dominant},
+                             if graph_mode else "eager launches bracketed by event pairs"
+                             if args.full else "eager launches"},
         }
+        if args.full:
+            result.update({
+                "first_pass_ms": round(first_pass_ms, 3),
+                "first_pass_ms_all": [round(t, 3) for t in first_passes],
+                "cold_process_first_pass_ms": round(cold_process_first_pass_ms, 3),
+                "first_pass": "first_pass_ms: this driver handed a NEW scene object (every per-scene "
+                              "structure rebuilt, then one pass; three scenes in a row, the median) -- "
+                              "what the reference's one-pass-per-scene caller pays per scene "
+                              "(scripts/forward_pass.py:120-142); cold_process: "
+                              "the process's very first pass (HIP module load, context, first-touch "
+                              "allocation on top).  Both outside the timed region.",
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "other_configs": other_configs,
+                "wall_s": {"imports_scene": round(t_wall["scene"] - t_wall["start"], 1),
+                           "warmup_breakdown_timed": round(t_wall["timed"] - t_wall["scene"], 1),
+                           "counter_passes": round(t_wall["counters"] - t_wall["timed"], 1),
+                           "config4": round(t_wall["config4"] - t_wall["counters"], 1),
+                           "cpu_baseline": round(time.perf_counter() - t_wall["config4"], 1)},
+                "kernels": kernels,
+                "ranks": ranks_report,
+                "kernel_events": {"breakdown_steps_untimed": breakdown_steps,
+                                  "timed_region": "all launches" if only is None else
+                                  "launches of %s only" % dominant},
+            })
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()

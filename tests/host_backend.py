@@ -40,8 +40,14 @@ class OracleBackend(object):
         return acc.reshape(self.grid_shape).clone()
 
     @staticmethod
-    def _unpack(vox):
+    def _unpack(vox, rvc):
+        """[n, M] packed voxel lists -> [n, M, 3] indices.  Entries at or past a row's count are 0,
+        as the oracle's traversal leaves them: the driver writes only the rows and entries a pass
+        uses, and its padding rows (count 0) hold whatever the buffer held -- the oracle's depth
+        read-out looks up entry 0 of a row whose distribution is all zero."""
         v = vox.numpy()
+        live = np.arange(v.shape[1])[None, :] < rvc.numpy()[:, None]
+        v = np.where(live, v, 0)
         return np.ascontiguousarray(np.stack([v >> 20, (v >> 10) & 1023, v & 1023], axis=-1)
                                     .astype(np.int32))
 
@@ -71,7 +77,7 @@ class OracleBackend(object):
             msgs.zero_()
         m = np.ascontiguousarray(msgs.numpy())
         out = np.ascontiguousarray(acc_part[0].numpy().reshape(self.grid_shape))
-        self.o.bp_sweep(Sr.numpy(), self._unpack(vox), rvc.numpy(),
+        self.o.bp_sweep(Sr.numpy(), self._unpack(vox, rvc), rvc.numpy(),
                         acc_in.numpy().reshape(self.grid_shape), m, out)
         msgs.numpy()[...] = m
         acc_part[0].numpy()[...] = out.ravel()
@@ -88,7 +94,7 @@ class OracleBackend(object):
         acc_part.zero_()
 
     def scene_depth(self, Sr, vox, rvc, acc, msgs, center, S_new, depth_map, rays_per_center=0):
-        rvi = self._unpack(vox)
+        rvi = self._unpack(vox, rvc)
         Sn = self.o.depth_distribution(Sr.numpy(), rvi, rvc.numpy(),
                                        acc.numpy().reshape(self.grid_shape), msgs.numpy())
         if S_new is not None:

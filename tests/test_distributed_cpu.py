@@ -6,6 +6,7 @@ its context from (perform_raynet_fp) with a host stand-in built on the oracle
 multi-GPU logic of forward_pass.py: contiguous ray sharding, zero-initialised local
 accumulators, ONE all-reduce per BP iteration with the prior added once after it
 (SURVEY.md 8e), and the merge of the per-rank depth slices."""
+import faulthandler
 import os
 import socket
 import sys
@@ -22,6 +23,9 @@ H, W, D, M, GRID, VIEWS = 12, 16, 8, 48, (16, 16, 16), 3
 
 
 def _run(rank, world, port, out_dir, filtered=False):
+    if world > 1:
+        # a crash in a spawned rank leaves its Python stack on stderr (captured with the test's output)
+        faulthandler.enable()
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tests"))
     from host_backend import OracleBackend

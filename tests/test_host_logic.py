@@ -250,7 +250,7 @@ def test_leases_taken_and_dropped_from_several_threads():
 
 
 def test_the_committed_bench_line_keeps_the_drivers_contract():
-    """The round's last bench line (profiles/, produced by `python bench.py` on an MI355X) carries what the
+    """The round's last bench line (profiles/, produced by `python bench.py --full` on an MI355X) carries what the
     driver's contract asks of the ONE JSON line -- metric / value / unit / n_gpus / steps / warmup /
     ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload -- plus the two
     objects of this tier, `roofline` and `cpu_baseline`, and its numbers agree with each other."""

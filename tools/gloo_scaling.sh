@@ -15,7 +15,7 @@ cd $R
 for N in 2 4 8; do
   RAYNET_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-    bench.py --gpus $N --steps 3 --warmup 1 --no-cpu-baseline 2>$OUT/${TAG}_gloo_$N.err \
+    bench.py --gpus $N --steps 3 --warmup 1 --full --no-cpu-baseline 2>$OUT/${TAG}_gloo_$N.err \
     | tail -1 >> $OUT/${TAG}_gloo_ranks.jsonl
   echo "N=$N rc=$?"
 done

@@ -10,7 +10,8 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   cat gpurun_out/${TAG}_pytest_gpu.log | tail -8
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  timeout 900 python bench.py --pmc off --no-cpu-baseline > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-  tail -c 3000 gpurun_out/${TAG}_bench.json
-  tail -5 gpurun_out/${TAG}_bench.err
+  OUT=${OUT:-/tmp/raynet_bench}; mkdir -p "$OUT"
+  timeout 900 python bench.py --full --pmc off --no-cpu-baseline > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+  tail -c 3000 "$OUT/${TAG}_bench.json"
+  tail -5 "$OUT/${TAG}_bench.err"
 fi

@@ -17,5 +17,6 @@ import csv
 rows=list(csv.DictReader(open("gpurun_out/${TAG}_kernel_stats_rocprofv3.csv")))
 for r in rows[:7]: print(r["Name"][:70], r["Calls"], r["AverageNs"], r["Percentage"])
 PY
-timeout 1500 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; tail -c 1500 gpurun_out/${TAG}_bench.json; tail -3 gpurun_out/${TAG}_bench.err
+OUT=${OUT:-/tmp/raynet_bench}; mkdir -p "$OUT"
+timeout 1500 python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"; tail -c 1500 "$OUT/${TAG}_bench.json"; tail -3 "$OUT/${TAG}_bench.err"
 NO_PROF=1 WORLDS=1,2,4,8 ALL_RANKS=1 timeout 900 python tools/shard_proxy.py > gpurun_out/${TAG}_shard_proxy_config2.txt 2>&1; grep -i "ceiling\|slowest" gpurun_out/${TAG}_shard_proxy_config2.txt | tail -6
