@@ -528,6 +528,42 @@ int rn_consistency_tau(rn_ctx *ctx, int32_t n, int32_t H, int32_t W, int32_t fir
 int rn_nearest_neighbors(rn_ctx *ctx, int32_t n_ref, const float *ref_xyzw, int32_t n_query,
                          const float *query_xyzw, float *dist, int32_t *idx, void *stream);
 
+/* ---- ground truth from scene meshes ----------------------------------------
+ * The reference casts one ray per pixel through an octree of the ground-truth mesh
+ * (common/scene.py:187-201, utils/oct_tree.py, utils/training_utils.py:194-220,
+ * utils/fast_utils.pyx:47-117).  Here a BVH is built on the GPU (LBVH: Morton keys sorted by
+ * the caller, Karras hierarchy, node boxes from the leaves' ranges) and traversed one lane
+ * per ray.  Triangles are [n][9] f32 rows p0 | p1 | p2; all buffers are device memory owned
+ * by the caller; nodes are [max(n-1, 1)][16] f32, leaves [n][12] f32. */
+
+/* Build step 1 (replaces OctTree.__init__, oct_tree.py:20-38): keys[i] = 30-bit Morton code
+ * of triangle i's centroid quantised in box (device, lo xyz | hi xyz) << 32 | i.  The caller
+ * sorts the keys (they are unique, so the order is fixed) and hands them to rn_mesh_build. */
+int rn_mesh_keys(rn_ctx *ctx, int32_t n, const float *triangles, const float *box,
+                 int64_t *keys, void *stream);
+
+/* Build step 2: leaves (p0, p1 - p0, p2 - p0, triangle index) in key order, the Karras
+ * hierarchy and both child boxes of every internal node.  work: 56*n + 64 bytes of device
+ * scratch.  Synchronises on `stream`; *depth_out (host) = depth of the deepest leaf;
+ * RN_ERR_INVALID if it exceeds the traversal stack (63). */
+int rn_mesh_build(rn_ctx *ctx, int32_t n, const float *triangles, const int64_t *sorted_keys,
+                  float *nodes, float *leaves, void *work, int32_t *depth_out, void *stream);
+
+/* get_ray_meshes_first_intersection (training_utils.py:194-220) for n rays: origins and
+ * destinations [n][3] f32 -> points [n][3] f32 (the first hit, t >= 0) and tri [n] (the
+ * original triangle index, -1 on a miss). */
+int rn_mesh_raycast(rn_ctx *ctx, int32_t n, const float *origins, const float *destinations,
+                    const float *nodes, const float *leaves, float *points, int32_t *tri,
+                    void *stream);
+
+/* RestrepoScene.get_depth_for_pixel (scene.py:187-201) for every pixel of an H x W image:
+ * the ray from camera_center [3] f32 to project(P_pinv, (u, v, 1)) (P_pinv [4][3] f32, the
+ * product formed in float64 and rounded once to f32); depth_map [H][W] f32 = distance of the
+ * hit to the centre, 0 where the ray hits nothing. */
+int rn_mesh_depthmap(rn_ctx *ctx, int32_t H, int32_t W, const float *P_pinv,
+                     const float *camera_center, const float *nodes, const float *leaves,
+                     float *depth_map, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -38,7 +38,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     pass for the shipped library (tests/test_abi.py)."""
     srcs = [os.path.join(CSRC, "raynet_hip.hip"), os.path.join(CSRC, "raynet_kernels.h"),
             os.path.join(CSRC, "raynet_prepare.inl"), os.path.join(CSRC, "raynet_mrf.inl"),
-            os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"), HEADER]
+            os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"),
+            os.path.join(CSRC, "raynet_mesh.inl"), HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
         # RAYNET_HIP_LIB names ANOTHER build of the library (a variant somebody made on purpose):
@@ -165,6 +166,10 @@ SIGNATURES = {
     "rn_depthmap_points": [_P, _I, _I, _P, _P, _P, _P, _P],
     "rn_consistency_tau": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "rn_nearest_neighbors": [_P, _I, _P, _I, _P, _P, _P, _P],
+    "rn_mesh_keys": [_P, _I, _P, _P, _P, _P],
+    "rn_mesh_build": [_P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(_I), _P],
+    "rn_mesh_raycast": [_P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_depthmap": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

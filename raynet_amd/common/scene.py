@@ -3,7 +3,8 @@
 `Scene` (in-memory images + cameras + bbox) carries the array conventions of the reference's
 raynet/common/scene.py:22-141; `RestrepoScene` and `DTUScene` read the two on-disk dataset
 layouts the reference supports (scene.py:144-452, parse_input_data.py:13-58), SURVEY.md 8(f)
-row 4.  Host-side parsing only -- nothing here touches the GPU.
+row 4.  Host-side parsing, except a Restrepo scene's mesh ground truth, which is ray-cast on the
+GPU (raynet_amd/mesh.py) the first time it is asked for.
 """
 import functools
 import os
@@ -197,7 +198,7 @@ def restrepo_cameras_scene(basepath, image_shape, n_images=None, channels=3, see
 
 class RestrepoScene(Scene):
     """A scene in the layout of Restrepo et al. (scene.py:144-254): imgs/, cams_krt/ (K, R, t
-    blocks), scene_info.xml (bbox), optionally gt/gt_depth_%d.npy."""
+    blocks), scene_info.xml (bbox), optionally gt/gt_depth_%d.npy and gt_mesh.obj / .ply."""
 
     def __init__(self, basepath, select_neighbors_based_on="filesystem"):
         super(RestrepoScene, self).__init__(select_neighbors_based_on=select_neighbors_based_on)
@@ -206,6 +207,8 @@ class RestrepoScene(Scene):
         self._cam_paths = self._load_sorted_files(basepath, "cams_krt")
         self._bbox_path = os.path.join(basepath, "scene_info.xml")
         self._cache = [None] * len(self._image_paths)
+        self._cache_depth_maps = [None] * len(self._image_paths)
+        self._raycaster = None
 
     n_images = property(lambda self: len(self._image_paths))
 
@@ -228,13 +231,49 @@ class RestrepoScene(Scene):
         f = os.path.join(self._basepath, "gt", "gt_depth_%d.npy" % (i,))
         return f if os.path.isfile(f) else None
 
+    def _get_raycaster(self):
+        """The ground-truth mesh's BVH, built once per scene (_get_oct_tree, scene.py:244-250);
+        NotImplementedError when the scene has no gt_mesh.obj / gt_mesh.ply."""
+        from .mesh_io import get_triangles, gt_mesh_file, parse_gt_data
+        if self._raycaster is None:
+            if gt_mesh_file(self._basepath) is None:
+                raise NotImplementedError("no gt_mesh.obj / gt_mesh.ply in %s" % self._basepath)
+            from ..mesh import MeshRaycaster
+            points, _, faces = parse_gt_data(self._basepath)
+            self._raycaster = MeshRaycaster(get_triangles(points, faces))
+        return self._raycaster
+
     def get_depth_map(self, i):
+        """gt/gt_depth_%d.npy if it exists, else the ground-truth mesh ray-cast on the GPU
+        (scene.py:117-125 + 187-201): [H, W] f32 distances to the camera centre, 0 where the
+        pixel's ray hits nothing."""
         f = self.get_depthmap_file(i)
-        if f is None:
-            # the reference ray-casts the ground-truth meshes through an octree here
-            # (scene.py:187-201); that training-data machinery is not part of this package
-            raise NotImplementedError("no gt/gt_depth_%d.npy in %s" % (i, self._basepath))
-        return np.load(f)
+        if f is not None:
+            return np.load(f)
+        if self._cache_depth_maps[i] is None:
+            raycaster = self._get_raycaster()
+            im = self.get_image(i)
+            self._cache_depth_maps[i] = raycaster.depth_map(
+                im.camera, im.height, im.width).cpu().numpy()
+        return self._cache_depth_maps[i]
+
+    def get_depth_for_pixels(self, i, ys, xs):
+        """float64 depths of pixels (ys[k], xs[k]) of image i, NaN where the ray misses: the
+        batched get_depth_for_pixel."""
+        return self._get_raycaster().depth_for_pixels(self.get_image(i).camera, ys, xs)
+
+    def get_depth_for_pixel(self, i, y, x):
+        """Distance of pixel (y, x)'s first mesh hit to the camera centre (a Python float), None
+        where the ray hits nothing (scene.py:187-201)."""
+        d = float(self._get_raycaster().depth_for_pixels(self.get_image(i).camera, [y], [x])[0])
+        return None if np.isnan(d) else d
+
+    def get_pointcloud(self):
+        """The ground-truth mesh's vertices (scene.py:252-254)."""
+        from ..pointcloud import Pointcloud
+        from .mesh_io import parse_gt_data
+        points, _, _ = parse_gt_data(self._basepath)
+        return Pointcloud(points.T)
 
 
 def parse_scene_info_dtu_dataset(scene_file):
@@ -270,6 +309,8 @@ class DTUScene(Scene):
             if os.path.isdir(os.path.join(basepath, depth_dir)) else [])
         self._cache = [None] * len(self._image_paths)
         self._cache_depth_maps = [None] * len(self._image_paths)
+        self._gt_stl_path = os.path.join(basepath, "Points", "stl",
+                                         "stl%03d_total.ply" % (scene_idx,))
 
     n_images = property(lambda self: len(self._image_paths))
 
@@ -320,6 +361,12 @@ class DTUScene(Scene):
             D = D * (gt != 0)
             self._cache_depth_maps[i] = D.astype(np.float32)
         return self._cache_depth_maps[i]
+
+    def get_pointcloud(self):
+        """The scan's STL point cloud, Points/stl/stl%03d_total.ply (scene.py:450-452)."""
+        from ..pointcloud import Pointcloud
+        from .mesh_io import parse_stl_file_to_pointcloud
+        return Pointcloud(parse_stl_file_to_pointcloud(self._gt_stl_path).T)
 
 
 def get_scene(dataset_type, basepath, *args, **kwargs):

@@ -1654,3 +1654,6 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 
 // depth maps -> point cloud -> accuracy / completeness, SURVEY.md 8f row 3
 #include "raynet_eval.inl"
+
+// ground-truth depth from scene meshes (BVH ray casting)
+#include "raynet_mesh.inl"

@@ -1,0 +1,453 @@
+// raynet_mesh.inl -- ground truth from scene meshes: the first intersection of rays with a
+// triangle mesh through a bounding volume hierarchy built on the GPU.  Included at the end of
+// raynet_hip.hip.
+//
+//   k_mesh_keys       30-bit Morton code of every triangle's centroid, quantised in the
+//                     mesh's box, as the 64-bit key `code << 32 | triangle index`
+//   k_mesh_leaves     the leaves in key order: p0, e1 = p1 - p0, e2 = p2 - p0 (fp32, the bits
+//                     raynet/utils/fast_utils.pyx:80-81 computes) and the triangle's index
+//   k_mesh_hierarchy  the Karras (2012) radix tree over the sorted keys, one triangle per leaf
+//   k_mesh_boxes      the two child boxes of every internal node: min / max over the child's
+//                     contiguous leaf range (one wavefront per node) -- exact, one launch and
+//                     no hand-off between workgroups
+//   k_mesh_depth      the tree's depth (the traversal stack's guard)
+//   k_mesh_raycast    first intersection of explicit rays (one lane per ray)
+//   k_mesh_depthmap   first intersection of every pixel's ray -> distance map
+//
+// The intersection test restates fast_ray_triangles_intersection (fast_utils.pyx:47-117,
+// Moeller-Trumbore) operation for operation in fp32 with correctly rounded division and
+// square root (the library builds with -ffp-contract=off and HIP's correctly rounded fp32
+// division / sqrt); the winner is the hit with the smallest fp32 key
+// ((hx-ox)^2 + (hy-oy)^2) + (hz-oz)^2, the lower triangle index on equal keys
+// (training_utils.py:194-220: argmin over candidates in index order).  Only hits with t >= 0
+// count; every hit counts (the reference keeps the first 100).  DESIGN.md section 14.
+
+namespace {
+
+constexpr int MESH_STACK = 64;            // traversal stack entries per lane: depth <= 63
+constexpr int MESH_RAY_BLOCK = 128;       // k_mesh_raycast / k_mesh_depthmap workgroup size
+constexpr uint32_t MESH_LEAF = 0x80000000u;
+// relative widening of the slab test (pruning only): a node is visited unless it is further
+// than this fraction of the scene's scale away from the ray -- rounding in the intersection
+// test moves a hit by a few ulps of these magnitudes, far less than this margin
+constexpr float MESH_MARGIN = 1e-4f;
+
+// internal node: the boxes of both children; child references in a_lo.w / b_lo.w (bits):
+// an internal node's index, or MESH_LEAF | leaf index
+struct MeshNode {
+    float4 a_lo, a_hi, b_lo, b_hi;
+};
+// leaf in key order: p0.w holds the original triangle index (bits)
+struct MeshLeaf {
+    float4 p0, e1, e2;
+};
+
+__device__ __forceinline__ uint32_t morton_spread10(uint32_t x) {
+    x &= 0x3ffu;
+    x = (x | (x << 16)) & 0x030000ffu;
+    x = (x | (x << 8)) & 0x0300f00fu;
+    x = (x | (x << 4)) & 0x030c30c3u;
+    x = (x | (x << 2)) & 0x09249249u;
+    return x;
+}
+
+__device__ __forceinline__ uint32_t morton_cell(float c, float lo, float hi) {
+    const float ext = hi - lo;
+    if (!(ext > 0.f)) return 0u;
+    const float q = fminf(fmaxf((c - lo) / ext * 1024.f, 0.f), 1023.f);    // NaN -> 0
+    return (uint32_t)q;
+}
+
+// keys[i] = morton(centroid of triangle i) << 32 | i; box = mesh lo xyz, hi xyz
+__global__ __launch_bounds__(BLOCK) void k_mesh_keys(int n, const float *__restrict__ tris,
+                                                     const float *__restrict__ box,
+                                                     unsigned long long *__restrict__ keys) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *t = tris + (size_t)9 * i;
+    uint32_t code = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float c = (t[k] + t[3 + k] + t[6 + k]) / 3.f;
+        code |= morton_spread10(morton_cell(c, box[k], box[3 + k])) << (2 - k);
+    }
+    keys[i] = ((unsigned long long)code << 32) | (unsigned long long)(uint32_t)i;
+}
+
+// leaves and their boxes (lo, hi) in key order
+__global__ __launch_bounds__(BLOCK) void k_mesh_leaves(int n, const float *__restrict__ tris,
+                                                       const unsigned long long *__restrict__ keys,
+                                                       MeshLeaf *__restrict__ leaves,
+                                                       float4 *__restrict__ leaf_box) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t idx = (uint32_t)(keys[i] & 0xffffffffull);
+    const float *t = tris + (size_t)9 * idx;
+    const float p0x = t[0], p0y = t[1], p0z = t[2];
+    const float p1x = t[3], p1y = t[4], p1z = t[5];
+    const float p2x = t[6], p2y = t[7], p2z = t[8];
+    MeshLeaf L;
+    L.p0 = make_float4(p0x, p0y, p0z, __uint_as_float(idx));
+    L.e1 = make_float4(p1x - p0x, p1y - p0y, p1z - p0z, 0.f);
+    L.e2 = make_float4(p2x - p0x, p2y - p0y, p2z - p0z, 0.f);
+    leaves[i] = L;
+    leaf_box[2 * (size_t)i] = make_float4(fminf(fminf(p0x, p1x), p2x), fminf(fminf(p0y, p1y), p2y),
+                                          fminf(fminf(p0z, p1z), p2z), 0.f);
+    leaf_box[2 * (size_t)i + 1] = make_float4(fmaxf(fmaxf(p0x, p1x), p2x),
+                                              fmaxf(fmaxf(p0y, p1y), p2y),
+                                              fmaxf(fmaxf(p0z, p1z), p2z), 0.f);
+}
+
+// common-prefix length of keys a and b (-1 outside the list); keys are unique
+__device__ __forceinline__ int mesh_delta(const unsigned long long *keys, int n, int a, int b) {
+    if (b < 0 || b >= n) return -1;
+    return __clzll(keys[a] ^ keys[b]);
+}
+
+// Karras (2012), Figure 4: internal node i covers leaves [first, last], split between `split`
+// and split + 1.  ranges[i] = (first, last, split); parent[] over the node ids 0 .. n_int - 1
+// (internal) and n_int + k (leaf k).  One leaf: one internal node over [0, 0].
+__global__ __launch_bounds__(BLOCK) void k_mesh_hierarchy(int n, int n_int,
+                                                          const unsigned long long *__restrict__ keys,
+                                                          int4 *__restrict__ ranges,
+                                                          int *__restrict__ parent) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_int) return;
+    if (i == 0) parent[0] = -1;
+    if (n == 1) {
+        ranges[0] = make_int4(0, 0, 0, 0);
+        parent[n_int] = 0;
+        return;
+    }
+    const int d = mesh_delta(keys, n, i, i + 1) > mesh_delta(keys, n, i, i - 1) ? 1 : -1;
+    const int dmin = mesh_delta(keys, n, i, i - d);
+    long long lmax = 2;
+    while (mesh_delta(keys, n, i, (int)(i + lmax * d)) > dmin) lmax *= 2;
+    long long l = 0;
+    for (long long t = lmax / 2; t >= 1; t /= 2)
+        if (mesh_delta(keys, n, i, (int)(i + (l + t) * d)) > dmin) l += t;
+    const int j = (int)(i + l * d);
+    const int dnode = mesh_delta(keys, n, i, j);
+    long long s = 0, t = l;
+    do {
+        t = (t + 1) / 2;
+        if (mesh_delta(keys, n, i, (int)(i + (s + t) * d)) > dnode) s += t;
+    } while (t > 1);
+    const int split = (int)(i + s * d + (d < 0 ? -1 : 0));
+    const int first = min(i, j), last = max(i, j);
+    ranges[i] = make_int4(first, last, split, 0);
+    parent[first == split ? n_int + split : split] = i;
+    parent[last == split + 1 ? n_int + split + 1 : split + 1] = i;
+}
+
+__device__ __forceinline__ void mesh_box_range(const float4 *__restrict__ leaf_box, int first,
+                                               int last, int lane, float4 &lo, float4 &hi) {
+    lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
+    hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
+    for (int k = first + lane; k <= last; k += WAVE) {
+        const float4 a = leaf_box[2 * (size_t)k], b = leaf_box[2 * (size_t)k + 1];
+        lo.x = fminf(lo.x, a.x); lo.y = fminf(lo.y, a.y); lo.z = fminf(lo.z, a.z);
+        hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z);
+    }
+#pragma unroll
+    for (int m = WAVE / 2; m >= 1; m /= 2) {
+        lo.x = fminf(lo.x, __shfl_xor(lo.x, m)); lo.y = fminf(lo.y, __shfl_xor(lo.y, m));
+        lo.z = fminf(lo.z, __shfl_xor(lo.z, m));
+        hi.x = fmaxf(hi.x, __shfl_xor(hi.x, m)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, m));
+        hi.z = fmaxf(hi.z, __shfl_xor(hi.z, m));
+    }
+}
+
+// one wavefront per internal node: both children's boxes over their leaf ranges
+__global__ __launch_bounds__(BLOCK) void k_mesh_boxes(int n_int, const int4 *__restrict__ ranges,
+                                                      const float4 *__restrict__ leaf_box,
+                                                      MeshNode *__restrict__ nodes) {
+    const int w = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    if (w >= n_int) return;                       // uniform per wavefront
+    const int4 r = ranges[w];
+    int a0 = r.x, a1 = r.z, b0 = r.z + 1, b1 = r.y;
+    if (r.x == r.y) b0 = b1 = r.x;                // one leaf: both children are leaf 0
+    MeshNode nd;
+    mesh_box_range(leaf_box, a0, a1, lane, nd.a_lo, nd.a_hi);
+    mesh_box_range(leaf_box, b0, b1, lane, nd.b_lo, nd.b_hi);
+    nd.a_lo.w = __uint_as_float(a0 == a1 ? (MESH_LEAF | (uint32_t)a0) : (uint32_t)r.z);
+    nd.b_lo.w = __uint_as_float(b0 == b1 ? (MESH_LEAF | (uint32_t)b0) : (uint32_t)(r.z + 1));
+    if (lane == 0) nodes[w] = nd;
+}
+
+// depth of the deepest leaf (edges from the root) -> atomicMax into *depth
+__global__ __launch_bounds__(BLOCK) void k_mesh_depth(int n, int n_int, const int *__restrict__ parent,
+                                                      int *depth) {
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    int d = 0;
+    if (k < n) {
+        int id = n_int + k;
+        // a well-formed tree reaches the root within 63 steps; the bound only ends the walk of
+        // a malformed one, whose depth then fails the guard
+        while (id > 0 && d <= 4 * MESH_STACK) {
+            id = parent[id];
+            d++;
+        }
+    }
+#pragma unroll
+    for (int m = WAVE / 2; m >= 1; m /= 2) d = max(d, __shfl_xor(d, m));
+    if (threadIdx.x % WAVE == 0) atomicMax(depth, d);
+}
+
+// one axis of the slab test: the ray's t interval inside [lo, hi]; a ray parallel to the axis
+// (r == 0) is either inside the (widened) slab for every t or for none
+__device__ __forceinline__ void mesh_axis(float lo, float hi, float o, float r, float inv, float m,
+                                          float &tn, float &tf, bool &in) {
+    if (r != 0.f) {
+        const float a = (lo - o) * inv, b = (hi - o) * inv;
+        tn = fmaxf(tn, fminf(a, b));
+        tf = fminf(tf, fmaxf(a, b));
+    } else if (o < lo - m || o > hi + m) {
+        in = false;
+    }
+}
+
+// slab test of a node box against the ray, the interval widened by `m` (plus a relative share
+// of its far end) on both sides; true if the box may hold a hit with 0 <= t <= lim
+__device__ __forceinline__ bool mesh_slab(float4 lo, float4 hi, float ox, float oy, float oz,
+                                          float rx, float ry, float rz, float ix, float iy,
+                                          float iz, float m, float lim, float &tnear) {
+    float tn = -INFINITY, tf = INFINITY;
+    bool in = true;
+    mesh_axis(lo.x, hi.x, ox, rx, ix, m, tn, tf, in);
+    mesh_axis(lo.y, hi.y, oy, ry, iy, m, tn, tf, in);
+    mesh_axis(lo.z, hi.z, oz, rz, iz, m, tn, tf, in);
+    const float mm = m + MESH_MARGIN * fabsf(tf);
+    tnear = tn;
+    return in && tn - mm <= tf + mm && tf + mm >= 0.f && tn - mm <= lim;
+}
+
+struct MeshBest {
+    float key;
+    int tri;          // original triangle index, -1: no hit
+    float hx, hy, hz;
+};
+
+// fast_ray_triangles_intersection's body for one triangle, then the argmin rule
+__device__ __forceinline__ void mesh_test_leaf(const MeshLeaf &L, float ox, float oy, float oz,
+                                               float rx, float ry, float rz, MeshBest &b) {
+    const float e1x = L.e1.x, e1y = L.e1.y, e1z = L.e1.z;
+    const float e2x = L.e2.x, e2y = L.e2.y, e2z = L.e2.z;
+    const float px = ry * e2z - rz * e2y, py = rz * e2x - rx * e2z, pz = rx * e2y - ry * e2x;
+    const float det = e1x * px + e1y * py + e1z * pz;
+    if (-1e-6f < det && det < 1e-6f) return;
+    const float inv = 1.f / det;
+    const float tx = ox - L.p0.x, ty = oy - L.p0.y, tz = oz - L.p0.z;
+    const float u = (tx * px + ty * py + tz * pz) * inv;
+    if (u < 0.f || u > 1.f) return;
+    const float qx = ty * e1z - tz * e1y, qy = tz * e1x - tx * e1z, qz = tx * e1y - ty * e1x;
+    const float v = (rx * qx + ry * qy + rz * qz) * inv;
+    if (v < 0.f || u + v > 1.f) return;
+    const float t = (e2x * qx + e2y * qy + e2z * qz) * inv;
+    if (!(t >= 0.f)) return;
+    const float hx = ox + t * rx, hy = oy + t * ry, hz = oz + t * rz;
+    const float dx = hx - ox, dy = hy - oy, dz = hz - oz;
+    const float key = dx * dx + dy * dy + dz * dz;
+    const int tri = (int)__float_as_uint(L.p0.w);
+    if (key < b.key || (key == b.key && tri < b.tri)) {
+        b.key = key;
+        b.tri = tri;
+        b.hx = hx;
+        b.hy = hy;
+        b.hz = hz;
+    }
+}
+
+// first hit of the ray from o towards dst; `stack` is this lane's first LDS stack entry
+// (entries MESH_RAY_BLOCK apart).  Nearer child first, the other one pushed.
+__device__ __forceinline__ MeshBest mesh_first_hit(float ox, float oy, float oz, float dx, float dy,
+                                                   float dz, const MeshNode *__restrict__ nodes,
+                                                   const MeshLeaf *__restrict__ leaves,
+                                                   uint32_t *stack) {
+    // ray = (dst - o) / sqrt(|dst - o|^2), fast_utils.pyx:56-63
+    float rx = dx - ox, ry = dy - oy, rz = dz - oz;
+    const float norm = sqrtf(rx * rx + ry * ry + rz * rz);
+    rx = rx / norm;
+    ry = ry / norm;
+    rz = rz / norm;
+    // slab test inputs (pruning only, no exactness needed; unused where a component is 0)
+    const float ix = 1.f / rx, iy = 1.f / ry, iz = 1.f / rz;
+    const MeshNode root = nodes[0];
+    const float scale = fmaxf(fmaxf(fmaxf(fabsf(root.a_lo.x), fabsf(root.a_lo.y)), fabsf(root.a_lo.z)),
+                              fmaxf(fmaxf(fabsf(root.a_hi.x), fabsf(root.a_hi.y)), fabsf(root.a_hi.z)));
+    const float scale_b = fmaxf(fmaxf(fmaxf(fabsf(root.b_lo.x), fabsf(root.b_lo.y)), fabsf(root.b_lo.z)),
+                                fmaxf(fmaxf(fabsf(root.b_hi.x), fabsf(root.b_hi.y)), fabsf(root.b_hi.z)));
+    const float m = MESH_MARGIN * (fmaxf(scale, scale_b) +
+                                   fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)));
+    MeshBest b;
+    b.key = INFINITY;
+    b.tri = -1;
+    b.hx = b.hy = b.hz = 0.f;
+    uint32_t node = 0;
+    int sp = 0;
+    while (true) {
+        const MeshNode nd = nodes[node];
+        const float lim = sqrtf(b.key) * (1.f + MESH_MARGIN) + m;
+        float ta, tb;
+        bool ha = mesh_slab(nd.a_lo, nd.a_hi, ox, oy, oz, rx, ry, rz, ix, iy, iz, m, lim, ta);
+        bool hb = mesh_slab(nd.b_lo, nd.b_hi, ox, oy, oz, rx, ry, rz, ix, iy, iz, m, lim, tb);
+        const uint32_t ca = __float_as_uint(nd.a_lo.w), cb = __float_as_uint(nd.b_lo.w);
+        if (ha && (ca & MESH_LEAF)) {
+            mesh_test_leaf(leaves[ca & ~MESH_LEAF], ox, oy, oz, rx, ry, rz, b);
+            ha = false;
+        }
+        if (hb && (cb & MESH_LEAF)) {
+            mesh_test_leaf(leaves[cb & ~MESH_LEAF], ox, oy, oz, rx, ry, rz, b);
+            hb = false;
+        }
+        if (ha && hb) {
+            const bool a_first = ta <= tb;
+            stack[sp * MESH_RAY_BLOCK] = a_first ? cb : ca;
+            sp++;
+            node = a_first ? ca : cb;
+        } else if (ha) {
+            node = ca;
+        } else if (hb) {
+            node = cb;
+        } else {
+            if (sp == 0) break;
+            sp--;
+            node = stack[sp * MESH_RAY_BLOCK];
+        }
+    }
+    return b;
+}
+
+// explicit rays: origins / destinations [n][3] f32 -> points [n][3] f32, tri [n] (-1: miss)
+__global__ __launch_bounds__(MESH_RAY_BLOCK) void k_mesh_raycast(int n, const float *__restrict__ origins,
+                                                                 const float *__restrict__ dests,
+                                                                 const MeshNode *__restrict__ nodes,
+                                                                 const MeshLeaf *__restrict__ leaves,
+                                                                 float *__restrict__ points,
+                                                                 int32_t *__restrict__ tri) {
+    __shared__ uint32_t stack[MESH_STACK * MESH_RAY_BLOCK];
+    const int i = blockIdx.x * MESH_RAY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t o = 3 * (size_t)i;
+    const MeshBest b = mesh_first_hit(origins[o], origins[o + 1], origins[o + 2], dests[o],
+                                      dests[o + 1], dests[o + 2], nodes, leaves,
+                                      stack + threadIdx.x);
+    points[o] = b.hx;
+    points[o + 1] = b.hy;
+    points[o + 2] = b.hz;
+    tri[i] = b.tri;
+}
+
+// pixel i = u*H + v (k_depth_points' order): ray from the centre to project(P_pinv, (u, v, 1))
+// formed in float64 from the fp32 P_pinv [4][3] and rounded once to fp32; depth [H][W] f32 =
+// distance of the hit to the centre (float64, then rounded), 0 where the ray hits nothing
+__global__ __launch_bounds__(MESH_RAY_BLOCK) void k_mesh_depthmap(int H, int W, const float *__restrict__ P_pinv,
+                                                                  const float *__restrict__ center,
+                                                                  const MeshNode *__restrict__ nodes,
+                                                                  const MeshLeaf *__restrict__ leaves,
+                                                                  float *__restrict__ depth) {
+    __shared__ uint32_t stack[MESH_STACK * MESH_RAY_BLOCK];
+    const int i = blockIdx.x * MESH_RAY_BLOCK + threadIdx.x;
+    if (i >= H * W) return;
+    const int u = i / H, v = i % H;
+    double r[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        r[k] = (double)P_pinv[3 * k] * (double)u + (double)P_pinv[3 * k + 1] * (double)v +
+               (double)P_pinv[3 * k + 2];
+    const float cx = center[0], cy = center[1], cz = center[2];
+    const MeshBest b = mesh_first_hit(cx, cy, cz, (float)(r[0] / r[3]), (float)(r[1] / r[3]),
+                                      (float)(r[2] / r[3]), nodes, leaves, stack + threadIdx.x);
+    float out = 0.f;
+    if (b.tri >= 0) {
+        const double ex = (double)b.hx - (double)cx, ey = (double)b.hy - (double)cy,
+                     ez = (double)b.hz - (double)cz;
+        out = (float)sqrt(ex * ex + ey * ey + ez * ez);
+    }
+    depth[(size_t)v * W + u] = out;
+}
+
+constexpr int MESH_MAX_TRIANGLES = 1 << 30;
+
+}  // namespace
+
+extern "C" {
+
+int rn_mesh_keys(rn_ctx *ctx, int32_t n, const float *triangles, const float *box,
+                 int64_t *keys, void *stream) {
+    if (!ctx || n < 1 || n > MESH_MAX_TRIANGLES || !triangles || !box || !keys)
+        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(k_mesh_keys, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, triangles,
+                       box, reinterpret_cast<unsigned long long *>(keys));
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mesh_build(rn_ctx *ctx, int32_t n, const float *triangles, const int64_t *sorted_keys,
+                  float *nodes, float *leaves, void *work, int32_t *depth_out, void *stream) {
+    if (!ctx || n < 1 || n > MESH_MAX_TRIANGLES || !triangles || !sorted_keys || !nodes ||
+        !leaves || !work || !depth_out)
+        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    const int n_int = n > 1 ? n - 1 : 1;
+    const auto *keys = reinterpret_cast<const unsigned long long *>(sorted_keys);
+    char *w = static_cast<char *>(work);
+    float4 *leaf_box = reinterpret_cast<float4 *>(w);                       // 32 n bytes
+    int4 *ranges = reinterpret_cast<int4 *>(w + 32 * (size_t)n);            // 16 n
+    int *parent = reinterpret_cast<int *>(w + 48 * (size_t)n);              // 8 n
+    int *depth = reinterpret_cast<int *>(w + 56 * (size_t)n);               // 4
+    RN_HIP(ctx, hipMemsetAsync(depth, 0, sizeof(int), S(stream)));
+    hipLaunchKernelGGL(k_mesh_leaves, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, triangles,
+                       keys, reinterpret_cast<MeshLeaf *>(leaves), leaf_box);
+    RN_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mesh_hierarchy, dim3(thread_blocks(n_int)), dim3(BLOCK), 0, S(stream), n,
+                       n_int, keys, ranges, parent);
+    RN_LAUNCH_CHECK(ctx);
+    const int waves_per_block = BLOCK / WAVE;
+    hipLaunchKernelGGL(k_mesh_boxes, dim3((n_int + waves_per_block - 1) / waves_per_block),
+                       dim3(BLOCK), 0, S(stream), n_int, ranges, leaf_box,
+                       reinterpret_cast<MeshNode *>(nodes));
+    RN_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mesh_depth, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, n_int,
+                       parent, depth);
+    RN_LAUNCH_CHECK(ctx);
+    int h = 0;
+    RN_HIP(ctx, hipMemcpyAsync(&h, depth, sizeof(int), hipMemcpyDeviceToHost, S(stream)));
+    RN_HIP(ctx, hipStreamSynchronize(S(stream)));
+    *depth_out = h;
+    // unique 62-bit keys bound the depth to 63; a deeper tree would overrun the stack
+    if (h > MESH_STACK - 1)
+        return fail(ctx, RN_ERR_INVALID, "BVH depth %d exceeds the traversal stack (%d)", h,
+                    MESH_STACK - 1);
+    return RN_OK;
+}
+
+int rn_mesh_raycast(rn_ctx *ctx, int32_t n, const float *origins, const float *destinations,
+                    const float *nodes, const float *leaves, float *points, int32_t *tri,
+                    void *stream) {
+    if (ctx && n == 0) return RN_OK;
+    if (!ctx || n < 0 || !origins || !destinations || !nodes || !leaves || !points || !tri)
+        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(k_mesh_raycast, dim3((n + MESH_RAY_BLOCK - 1) / MESH_RAY_BLOCK),
+                       dim3(MESH_RAY_BLOCK), 0, S(stream), n, origins, destinations,
+                       reinterpret_cast<const MeshNode *>(nodes),
+                       reinterpret_cast<const MeshLeaf *>(leaves), points, tri);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mesh_depthmap(rn_ctx *ctx, int32_t H, int32_t W, const float *P_pinv,
+                     const float *camera_center, const float *nodes, const float *leaves,
+                     float *depth_map, void *stream) {
+    if (!ctx || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30 || !P_pinv ||
+        !camera_center || !nodes || !leaves || !depth_map)
+        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(k_mesh_depthmap, dim3((H * W + MESH_RAY_BLOCK - 1) / MESH_RAY_BLOCK),
+                       dim3(MESH_RAY_BLOCK), 0, S(stream), H, W, P_pinv, camera_center,
+                       reinterpret_cast<const MeshNode *>(nodes),
+                       reinterpret_cast<const MeshLeaf *>(leaves), depth_map);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+}  // extern "C"

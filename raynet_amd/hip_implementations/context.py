@@ -360,6 +360,50 @@ class HipContext(object):
 
     KERNEL_NAMES = {1: "traverse", 2: "sweep_map", 3: "bp", 4: "depth", 5: "acc", 6: "other", 7: "scatter"}
 
+    # ---- ground truth from scene meshes (raynet_amd/mesh.py) ----------------------------
+    def mesh_keys(self, triangles, box, keys):
+        n = triangles.shape[0]
+        _chk(triangles, torch.float32, 9 * n, "triangles")
+        _chk(box, torch.float32, 6, "box")
+        _chk(keys, torch.int64, n, "keys", align=8)
+        self._check(self.lib.rn_mesh_keys(self._h, n, _ptr(triangles), _ptr(box), _ptr(keys),
+                                          _stream()))
+
+    def mesh_build(self, triangles, sorted_keys, nodes, leaves, work):
+        """Leaves, hierarchy and node boxes; returns the tree's depth (synchronises)."""
+        n = triangles.shape[0]
+        _chk(triangles, torch.float32, 9 * n, "triangles")
+        _chk(sorted_keys, torch.int64, n, "sorted_keys", align=8)
+        _chk(nodes, torch.float32, 16 * max(n - 1, 1), "nodes", align=16)
+        _chk(leaves, torch.float32, 12 * n, "leaves", align=16)
+        _chk(work, torch.uint8, 56 * n + 64, "work", align=16)
+        depth = ctypes.c_int32(0)
+        self._check(self.lib.rn_mesh_build(self._h, n, _ptr(triangles), _ptr(sorted_keys),
+                                           _ptr(nodes), _ptr(leaves), _ptr(work),
+                                           ctypes.byref(depth), _stream()))
+        return int(depth.value)
+
+    def mesh_raycast(self, origins, destinations, nodes, leaves, points, tri):
+        n = origins.shape[0]
+        for name, t in (("origins", origins), ("destinations", destinations), ("points", points)):
+            _chk(t, torch.float32, 3 * n, name)
+        _chk(tri, torch.int32, n, "tri")
+        _chk(nodes, torch.float32, 16, "nodes", align=16)
+        _chk(leaves, torch.float32, 12, "leaves", align=16)
+        self._check(self.lib.rn_mesh_raycast(self._h, n, _ptr(origins), _ptr(destinations),
+                                             _ptr(nodes), _ptr(leaves), _ptr(points), _ptr(tri),
+                                             _stream()))
+
+    def mesh_depthmap(self, H, W, P_pinv, center, nodes, leaves, depth_map):
+        _chk(P_pinv, torch.float32, 12, "P_pinv")
+        _chk(center, torch.float32, 3, "center")
+        _chk(nodes, torch.float32, 16, "nodes", align=16)
+        _chk(leaves, torch.float32, 12, "leaves", align=16)
+        _chk(depth_map, torch.float32, int(H) * int(W), "depth_map")
+        self._check(self.lib.rn_mesh_depthmap(self._h, int(H), int(W), _ptr(P_pinv), _ptr(center),
+                                              _ptr(nodes), _ptr(leaves), _ptr(depth_map),
+                                              _stream()))
+
     def prof_begin(self, capacity=4096, only=None):
         """only: kernel family names to bracket (None = all of them)."""
         mask = 0xFFFFFFFF

@@ -99,3 +99,30 @@ def make_synthetic_scene(H=480, W=640, n_views=5, F=32, padding=11,
     bank = FeatureBank(planted_feature_maps(cams, H, W, F=F, padding=padding, seed=seed,
                                             device=device))
     return scene, bank
+
+
+def make_box_city(n_triangles, bbox=(-5.0, -5.0, -0.7, 5.0, 5.0, 1.5), seed=0):
+    """A synthetic "city" triangle soup [T, 9] f32 (T <= n_triangles): a ground quad at the
+    bottom of `bbox` and axis-aligned boxes standing on it (12 triangles each) of random
+    footprints and heights -- the stand-in for a scene's ground-truth mesh in the ray-casting
+    tests and tools/raycast_bench.py."""
+    rng = np.random.default_rng(seed)
+    x0, y0, z0, x1, y1, z1 = [float(b) for b in bbox]
+    n_boxes = max(0, (int(n_triangles) - 2) // 12)
+    ground = np.array([[x0, y0, z0, x1, y0, z0, x1, y1, z0],
+                       [x0, y0, z0, x1, y1, z0, x0, y1, z0]], np.float32)
+    # footprints shrink with the number of boxes so that the city stays about as dense
+    side = (x1 - x0) / max(1.0, np.sqrt(n_boxes)) * 0.8
+    cx = rng.uniform(x0 + side, x1 - side, n_boxes)
+    cy = rng.uniform(y0 + side, y1 - side, n_boxes)
+    hx = rng.uniform(0.15, 0.5, n_boxes) * side
+    hy = rng.uniform(0.15, 0.5, n_boxes) * side
+    top = z0 + rng.uniform(0.05, 1.0, n_boxes) * (z1 - z0)
+    corners = np.stack([
+        np.stack([cx + sx * hx, cy + sy * hy, np.where(sz > 0, top, z0)], axis=1)
+        for sz in (-1, 1) for sy in (-1, 1) for sx in (-1, 1)], axis=1)     # [B, 8, 3]
+    # corner k = x-bit | y-bit << 1 | z-bit << 2; two triangles per face
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    faces = [(a, b, c) for q in quads for (a, b, c) in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))]
+    boxes = corners[:, np.array(faces).reshape(-1)].reshape(n_boxes * 12, 9)
+    return np.ascontiguousarray(np.concatenate([ground, boxes.astype(np.float32)]))

@@ -71,6 +71,40 @@ def one_hot_target(voxel_of_point, ray_voxel_indices, ray_voxel_count):
     return target
 
 
+def target_points_for_rays(scene, ref_idx, ray_idxs):
+    """The ground-truth surface point of every ray of `ray_idxs` (pixel i = u*H + v) of image
+    `ref_idx`: (points [n, 3] f32, valid [n] bool), by the rule of
+    raynet/train_network/sample.py:162-190 -- a ray whose depth is missing (its ray hits no
+    ground-truth surface) or 0 is invalid; otherwise its point is
+    point_from_depth(centre, ray - centre, depth) (generic_utils.py:32-60, fp32), and the ray
+    is invalid if that point lies outside the scene's bbox.  Depths come from the scene's
+    get_depth_for_pixels (a mesh ray-cast) where it has one, else from its depth map.
+    Invalid rays' points are 0.  The result feeds get_batch_of_rays' `target_points`."""
+    H, W = scene.image_shape
+    ridx = np.asarray(ray_idxs, dtype=np.int64).reshape(-1)
+    u, v = ridx // H, ridx % H
+    if hasattr(scene, "get_depth_for_pixels"):
+        depth = np.asarray(scene.get_depth_for_pixels(ref_idx, v, u), dtype=np.float64)
+    else:
+        depth = np.asarray(scene.get_depth_map(ref_idx), dtype=np.float64)[v, u]
+    valid = np.isfinite(depth) & (depth != 0)
+    cam = scene.get_image(ref_idx).camera
+    f32 = np.float32
+    # Image.ray (common/image.py:210-240): project(P_pinv, (x, y, 1)) in fp32
+    pix = np.stack([u, v, np.ones_like(u)]).astype(np.int32).astype(f32)
+    ray = np.dot(np.asarray(cam.P_pinv, dtype=f32), pix)
+    ray = ray / ray[-1:]
+    c = np.asarray(cam.center, dtype=f32).reshape(-1, 1)[:3]
+    a = ray[:3] - c
+    a_norm = a / np.sqrt(np.sum(a ** 2, axis=0, keepdims=True))
+    points = (a_norm * np.where(valid, depth, 0.0).astype(f32) + c).T.astype(f32)
+    bbox = np.asarray(scene.bbox, dtype=f32).reshape(6)
+    inside = np.all(points >= bbox[:3], axis=1) & np.all(points <= bbox[3:], axis=1)
+    valid &= inside
+    points[~valid] = 0
+    return points, valid
+
+
 def get_batch_of_rays(scene, ref_idx, ray_idxs, generation_params, hip, images, target_points,
                       patch_shape=(11, 11), reject_border_rays=True, return_valid=False):
     """The reference's `inputs` list for the rays of `ray_idxs` of reference image `ref_idx`.
