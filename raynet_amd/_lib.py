@@ -37,6 +37,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     another path; the flags end up in rn_version() (RN_BUILD_EXTRA), so a variant can never
     pass for the shipped library (tests/test_abi.py)."""
     srcs = [os.path.join(CSRC, "raynet_hip.hip"), os.path.join(CSRC, "raynet_kernels.h"),
+            os.path.join(CSRC, "raynet_launch.inl"), os.path.join(CSRC, "raynet_box_policy.h"),
             os.path.join(CSRC, "raynet_prepare.inl"), os.path.join(CSRC, "raynet_mrf.inl"),
             os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"),
             os.path.join(CSRC, "raynet_mesh.inl"), HEADER]

@@ -144,9 +144,7 @@ int rn_depthmap_points(rn_ctx *ctx, int32_t H, int32_t W, const double *P_pinv,
 int rn_consistency_tau(rn_ctx *ctx, int32_t n, int32_t H, int32_t W, int32_t first,
                        const double *points, const double *P, const double *camera_center,
                        const float *depth_map, double *tau, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || H < 1 || W < 1 || !points || !P || !camera_center || !depth_map || !tau)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, H >= 1 && W >= 1 && all_set(points, P, camera_center, depth_map, tau));
     hipLaunchKernelGGL(k_consistency_tau, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, H, W,
                        first, points, P, camera_center, depth_map, tau);
     RN_LAUNCH_CHECK(ctx);

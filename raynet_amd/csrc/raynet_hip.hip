@@ -1,20 +1,25 @@
 // raynet_hip.hip -- __global__ kernels and the C ABI (include/raynet_hip.h) of the
 // RayNet forward_pass hot path for MI355X / gfx950.  No CPU fallback lives here.
+// One translation unit: device helpers and small kernels, the kernel files, the host launch
+// layer (raynet_launch.inl), then the ABI entries.
 #include "raynet_kernels.h"
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
+#include <iterator>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "../../include/raynet_hip.h"
+#include "raynet_box_policy.h"
 
 using namespace rn;
 
 namespace {
 
 constexpr int BLOCK = 256;               // 4 wavefronts = 4 rays per workgroup
-constexpr int BOX_PROBE_LAUNCHES = 12;   // scatter launches after a reset whose overflow counters are read back
 constexpr int RAY_BLOCK = 256;           // threads per workgroup of the wave-per-ray MRF kernels (k_bp, k_depth)
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;
 // The plane sweep's own workgroup size.  The hardware deals consecutive
@@ -40,10 +45,12 @@ constexpr int NXCD = 8;
 // became non-temporal; re-measured after that, chunks of 256 - 1024 rays -- one to four 16 x 16
 // pixel tiles -- are 1.5 % faster at config 2 and 6.5 % at config 4, 64 rays are slower, 16384
 // much slower.)
-#define RN_XCD_CHUNK_SWEEP (2048 * 64 / 256)      /* workgroups: 2048 rays */
-#define RN_XCD_CHUNK_BP 256
-#define RN_XCD_CHUNK_DEPTH 1024    /* (contiguous eighths until round 6: config 4's k_depth 2.50 -> 2.32 ms per step with chunks of 1024 workgroups, config 2 within noise -- profiles/r06_l_variants_probe.txt) */
-#define RN_XCD_CHUNK_SCATTER 8
+constexpr int XCD_CHUNK_SWEEP = 2048 * 64 / 256;      // workgroups: 2048 rays
+constexpr int XCD_CHUNK_BP = 256;
+// (contiguous eighths until round 6: config 4's k_depth 2.50 -> 2.32 ms per step with chunks of
+// 1024 workgroups, config 2 within noise -- profiles/r06_l_variants_probe.txt)
+constexpr int XCD_CHUNK_DEPTH = 1024;
+constexpr int XCD_CHUNK_SCATTER = 8;
 template <int CHUNK = 0>
 __device__ __forceinline__ int xcd_block(int b, int nblocks) {
     if (CHUNK > 0) {
@@ -230,464 +237,8 @@ __global__ void k_add_scalar(float *a, int64_t n, float v) {
 
 }  // namespace
 
-// =============================================================== host side
-struct rn_ctx {
-    rn_config cfg;
-    Params p;
-    float *axes;          // device, gx+gy+gz
-    bool have_axes;
-    int scatter_mode;     // rn_options: -1 by row layout (default), 0 slab, 2 LDS box
-    int generic_sweep;    // rn_options: reference-order plane sweep even for F = 32
-    int sweep_rpw;        // rn_options.sweep_rays_per_wave: 0 by D, 1 one ray per wavefront
-    // LDS-box scatter: level in use (launch_bp), {chunks, overflowed chunks} of the previous
-    // launches on the device and its pinned host mirror
-    int box_level, box_level0;
-    bool box_pin;         // RAYNET_HIP_BOX_PIN: stay at the starting level (A/B runs)
-    // device counters {chunks, overflowed chunks}, cumulative over launches; their pinned host
-    // mirror (an asynchronous copy, it may lag a launch); what the launcher had seen of them at
-    // its previous look; the difference = the launches in between (rn_scatter_state), and how
-    // many more launches copy the counters out: the tile shape settles within the first
-    // launches after a reset, and two 8-byte operations behind every scatter are two more
-    // dependent items on a stream whose kernels take 70 us each on an eight-rank shard
-    unsigned *box_stats, *box_stats_host;
-    unsigned box_seen[2], box_obs[2];
-    int box_probe;
-    bool box_probe_used;  // some scatter has run since the context was created
-    bool box_rebase;      // after a reset: the next counters that arrive are a baseline, not an observation
-    // occupancy_to_ray(prior, 0) as the device evaluates it, for the prior it was last asked for
-    float first_prior, first_occ;
-    bool have_first_occ;
-    float *scalar_dev;        // 4 bytes of device scratch owned by the context
-    hipEvent_t ev0, ev1;
-    // second stream of the resident-scene launchers (RAYNET_HIP_OVERLAP=0 / 1, default: by
-    // the scatter's tile level): the accumulator scatter of one half of a launch's rows runs
-    // next to the BP sweep of the other half, the traversal of half of the images next to the
-    // plane sweep of the rest.  Measured (profiles/r02_exp_overlap.txt): config 2 8.72 ->
-    // 8.84 ms/step (either kernel alone already keeps the VALUs of every CU busy), config 4
-    // 44.3 -> 42.5 (its scatter waits on L2 atomics at 3.9 hits per voxel) -- and config 4 is
-    // where the adaptive scatter has stepped to its second tile shape, so that is the switch
-    // slab boxes (rn_scene_bind_slab_boxes): table, the list buffer it describes, and the row
-    // range rn_scene_prepare_all last filled
-    const int32_t *sb_vox;
-    int64_t sb_rows, sb_valid_lo, sb_valid_hi;
-    int2 *sb_boxes;
-    // work list of the box scatter (rn_scene_bind_scatter_items): the row range and tile level it
-    // was built for
-    const int32_t *sc_vox, *sc_items;
-    int64_t sc_rows;
-    int sc_level, sc_count;
-    int overlap;          // 0 off, 1 on, 2 (default) when the scatter runs at tile level >= 1
-    hipStream_t aux;
-    hipEvent_t ev_fork, ev_join;
-    // per-launch profiling (rn_prof_begin / rn_prof_end)
-    bool prof_on;
-    uint32_t prof_mask;       // which rn_kernel_id families are bracketed (rn_prof_select)
-    int prof_cap, prof_n;
-    hipEvent_t *prof_ev;      // 2 * prof_cap
-    int32_t *prof_id, *prof_rays;
-    // a failed opt-in to more than 64 KB of dynamic LDS (launch_sweep_t), reported by the launch check
-    hipError_t lds_optin_error;
-    size_t lds_optin_bytes;
-    char err[512];
-};
-
-// Brackets one kernel launch with two events on its stream when profiling is on.
-struct ProfScope {
-    rn_ctx *c;
-    hipStream_t st;
-    int slot;
-    ProfScope(rn_ctx *ctx, int id, int n_rays, hipStream_t s) : c(ctx), st(s), slot(-1) {
-        if (c->prof_on && ((c->prof_mask >> id) & 1u) && c->prof_n < c->prof_cap) {
-            slot = c->prof_n++;
-            c->prof_id[slot] = id;
-            c->prof_rays[slot] = n_rays;
-            (void)hipEventRecord(c->prof_ev[2 * slot], st);
-        }
-    }
-    ~ProfScope() {
-        if (slot >= 0) (void)hipEventRecord(c->prof_ev[2 * slot + 1], st);
-    }
-};
-
-namespace {
-
-int fail(rn_ctx *ctx, int code, const char *fmt, ...) {
-    if (ctx) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(ctx->err, sizeof(ctx->err), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
-#define RN_HIP(ctx, call)                                                              \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(ctx, RN_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-#define RN_LAUNCH_CHECK(ctx)                                                           \
-    do {                                                                               \
-        hipError_t e_ = hipGetLastError();                                             \
-        if ((ctx)->lds_optin_error != hipSuccess) {                                    \
-            const hipError_t o_ = (ctx)->lds_optin_error;                              \
-            (ctx)->lds_optin_error = hipSuccess;                                       \
-            return fail(ctx, RN_ERR_HIP, "the plane sweep's opt-in to %zu bytes of LDS "  \
-                        "(hipFuncSetAttribute) failed: %s; its launch: %s",            \
-                        (ctx)->lds_optin_bytes, hipGetErrorString(o_), hipGetErrorString(e_)); \
-        }                                                                              \
-        if (e_ != hipSuccess)                                                          \
-            return fail(ctx, RN_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e_)); \
-    } while (0)
-
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline int ray_blocks(int n) { return (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK; }
-inline int ray_blocks_mrf(int n) { return (n + RAY_BLOCK / WAVE - 1) / (RAY_BLOCK / WAVE); }
-inline int thread_blocks(int n) { return (n + BLOCK - 1) / BLOCK; }
-inline int fill_blocks(int64_t n) {
-    int64_t b = (n + BLOCK - 1) / BLOCK;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-inline size_t sweep_lds(const Params &p, int rows = 1) {
-    return sizeof(float) * ((size_t)((p.gx + p.gy + p.gz + 3) & ~3) + (size_t)((p.D + 4) & ~3) +
-                            (size_t)SWEEP_WAVES * (p.D + (size_t)rows * p.M));
-}
-inline int sweep_blocks(int n) { return (n + SWEEP_WAVES - 1) / SWEEP_WAVES; }
-// rays a wavefront of the cooperative sweep takes (k_sweep_map_packed for 2 / 4)
-inline int sweep_rays_per_wave(const rn_ctx *ctx) {
-    if (ctx->sweep_rpw == 1) return 1;
-    return ctx->p.D <= 16 ? 4 : ctx->p.D <= 32 ? 2 : 1;
-}
-
-// floats of one resident (bricked) accumulator: every axis padded to a multiple of 4
-inline int64_t acc_floats(const rn_ctx *ctx) {
-    return (int64_t)((ctx->p.gx + 3) / 4) * ctx->p.nby * ctx->p.nbz * 64;
-}
-
-FeatureViews stacked_views(const Params &p, const float *features) {
-    FeatureViews fv;
-    const size_t dim = (size_t)p.Hf * p.Wf * p.F;
-    for (int v = 0; v < MAX_VIEWS; v++) fv.v[v] = v < p.N ? features + dim * v : nullptr;
-    return fv;
-}
-
-inline void lds_opt_in(rn_ctx *ctx, const void *kernel, size_t lds, size_t &granted) {
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-        granted = lds;
-    } else {
-        (void)hipGetLastError();
-        ctx->lds_optin_error = e;
-        ctx->lds_optin_bytes = lds;
-    }
-}
-
-struct SweepArgs {
-    int n;
-    const int32_t *ray_idxs;
-    FeatureViews fv;
-    const float *P, *P_inv, *cc, *starts, *ends, *S_in;
-    const int32_t *vox, *rvc;
-    float *S_planes, *S_voxel, *depth_from_planes, *points;
-    const int32_t *order = nullptr;
-    // scene-wide launch (rn_scene_prepare_all): one grid row per reference image
-    const float *const *fv_table = nullptr;
-    int cam_stride = 0;
-    int64_t rows_per_image = 0;
-    int n_images = 1;
-    const float *seg = nullptr;     // [rows][8]: ray segments written by k_traverse
-    float *msgs_out = nullptr;      // MAPMODE 3: BP iteration 0's messages
-    float prior = 0.0f;             // MAPMODE 3: occupancy_to_ray(prior, 0), see first_occupancy()
-    float *zero = nullptr;          // MAPMODE 3: cleared on the side (rn_acc_size floats)
-    int xcd_chunk = 0;              // workgroups per XCD group (0: RN_XCD_CHUNK_SWEEP)
-};
-
-template <int SIM, int NV, int LPS, int MAPMODE, bool PACKED>
-void launch_sweep_t(rn_ctx *ctx, const SweepArgs &a, hipStream_t st) {
-    ProfScope prof(ctx, RN_K_SWEEP_MAP, a.n * a.n_images, st);
-    const size_t lds = sweep_lds(ctx->p, MAPMODE == 3 ? 3 : 1);
-    // gfx950 has 160 KB per CU; beyond 64 KB a kernel has to say so -- once per instantiation and
-    // size (one process drives one GPU), and a refusal is kept for the launch check to report
-    static size_t granted = 64 * 1024;
-    if (lds > granted)
-        lds_opt_in(ctx, (const void *)k_sweep_map<SIM, NV, LPS, MAPMODE, PACKED>, lds, granted);
-    hipLaunchKernelGGL((k_sweep_map<SIM, NV, LPS, MAPMODE, PACKED>),
-                       dim3(sweep_blocks(a.n), a.n_images), dim3(SWEEP_BLOCK), lds, st,
-                       ctx->p, a.n, a.ray_idxs, a.fv, a.P, a.P_inv, a.cc, a.starts, a.ends, a.S_in,
-                       ctx->axes, a.vox, a.rvc, a.S_planes, a.S_voxel, a.depth_from_planes,
-                       a.points, a.order, a.fv_table, a.cam_stride, a.rows_per_image, a.seg,
-                       a.msgs_out, a.prior, reinterpret_cast<float4 *>(a.zero),
-                       a.zero ? (int)(acc_floats(ctx) / 4) : 0, a.xcd_chunk);
-}
-
-// k_sweep_map_packed: RPW rays per wavefront (D <= 64 / RPW)
-inline size_t sweep_lds_packed(const Params &p, int rows, int rpw) {
-    return sizeof(float) * ((size_t)((p.gx + p.gy + p.gz + 3) & ~3) + (size_t)((p.D + 4) & ~3) +
-                            (size_t)SWEEP_WAVES * ((size_t)rpw * p.D + (size_t)rows * p.M));
-}
-template <int NV, int LPS, int MAPMODE, bool PACKED, int RPW>
-void launch_sweep_packed_t(rn_ctx *ctx, const SweepArgs &a, hipStream_t st) {
-    ProfScope prof(ctx, RN_K_SWEEP_MAP, a.n * a.n_images, st);
-    const size_t lds = sweep_lds_packed(ctx->p, MAPMODE == 3 ? 3 : 1, RPW);
-    static size_t granted = 64 * 1024;
-    if (lds > granted)
-        lds_opt_in(ctx, (const void *)k_sweep_map_packed<NV, LPS, MAPMODE, PACKED, RPW>, lds, granted);
-    const int nwaves = (a.n + RPW - 1) / RPW;
-    hipLaunchKernelGGL((k_sweep_map_packed<NV, LPS, MAPMODE, PACKED, RPW>),
-                       dim3(sweep_blocks(nwaves), a.n_images), dim3(SWEEP_BLOCK), lds, st,
-                       ctx->p, a.n, a.ray_idxs, a.fv, a.P, a.P_inv, a.cc, a.starts, a.ends,
-                       ctx->axes, a.vox, a.rvc, a.S_planes, a.S_voxel, a.depth_from_planes,
-                       a.points, a.order, a.fv_table, a.cam_stride, a.rows_per_image, a.seg,
-                       a.msgs_out, a.prior, reinterpret_cast<float4 *>(a.zero),
-                       a.zero ? (int)(acc_floats(ctx) / 4) : 0,
-                       a.xcd_chunk > 0 ? (a.xcd_chunk + RPW - 1) / RPW : 0);
-}
-
-// pick the plane-sweep flavour: cooperative for F=32 and 2..9 views (two / four rays per
-// wavefront for D <= 32 / 16 unless rn_options.sweep_rays_per_wave says 1), generic otherwise
-template <int MAPMODE, bool PACKED>
-void launch_sweep(rn_ctx *ctx, const SweepArgs &a, bool have_features, hipStream_t st) {
-    const Params &p = ctx->p;
-    if (!have_features) {
-        launch_sweep_t<0, 1, 8, MAPMODE, PACKED>(ctx, a, st);
-        return;
-    }
-    if (p.F == 32 && !ctx->generic_sweep) {
-        const int rpw = sweep_rays_per_wave(ctx);
-        switch (p.N) {
-#define RN_CASE(NV_)                                                  \
-    case NV_:                                                         \
-        if (rpw == 4)                                                 \
-            launch_sweep_packed_t<NV_, 8 / SWEEP_V4, MAPMODE, PACKED, 4>(ctx, a, st);   \
-        else if (rpw == 2)                                            \
-            launch_sweep_packed_t<NV_, 8 / SWEEP_V4, MAPMODE, PACKED, 2>(ctx, a, st);   \
-        else                                                          \
-            launch_sweep_t<2, NV_, 8 / SWEEP_V4, MAPMODE, PACKED>(ctx, a, st);       \
-        return;
-            RN_CASE(2) RN_CASE(3) RN_CASE(4) RN_CASE(5) RN_CASE(6) RN_CASE(7) RN_CASE(8) RN_CASE(9)
-#undef RN_CASE
-            default: break;
-        }
-    }
-    launch_sweep_t<1, 1, 8, MAPMODE, PACKED>(ctx, a, st);
-}
-
-// the slab-box rows that describe `vox` (a pointer into the bound list buffer), or null
-inline int2 *slab_boxes_for(const rn_ctx *ctx, const int32_t *vox, int64_t n, bool need_valid) {
-    if (!ctx->sb_boxes || !vox || vox < ctx->sb_vox) return nullptr;
-    const int64_t off = vox - ctx->sb_vox;
-    if (off % ctx->p.M) return nullptr;
-    const int64_t row0 = off / ctx->p.M;
-    if (row0 % WAVE || row0 + n > ctx->sb_rows) return nullptr;
-    if (need_valid && (row0 < ctx->sb_valid_lo || row0 + n > ctx->sb_valid_hi)) return nullptr;
-    return ctx->sb_boxes + (row0 / WAVE) * slab_box_count(ctx->p.M);
-}
-
-// workgroups per box-scatter tile (grid.y): enough of them for ~16 per CU
-inline int box_split(int n, int tile_rays) {
-    const int tiles = (n + tile_rays - 1) / tile_rays;
-#define RN_BOX_SPLIT_TARGET 4096
-#define RN_BOX_SPLIT_MAX 4
-    // (RAYNET_HIP_BOX_SPLIT="target,max": A/B override, read once)
-    static int target = 0, most = 0;
-    if (!target) {
-        target = RN_BOX_SPLIT_TARGET;
-        most = RN_BOX_SPLIT_MAX;
-        if (const char *e = getenv("RAYNET_HIP_BOX_SPLIT")) (void)sscanf(e, "%d,%d", &target, &most);
-        if (target < 1) target = 1;
-        if (most < 1) most = 1;
-    }
-    return max(1, min(most, target / max(tiles, 1)));
-}
-
-// One BP sweep: k_bp (messages) + the accumulator scatter that fits the row layout.
-// how a sweep reads its accumulator and what it clears on the side (the plan path, rn_scene_run)
-struct AccMode {
-    bool uniform = false;      // every voxel holds acc_in[0]
-    bool biased = false;       // acc_in holds sums only: the prior `bias` is added at the gather
-    float bias = 0.0f;
-    float *zero = nullptr;     // cleared by the FIRST k_bp launch of this call (rn_acc_size floats)
-};
-
-template <bool PACKED, bool CLIP_IN>
-void launch_bp_kernel(rn_ctx *ctx, int n, const float *Sv, const int32_t *vox, const int32_t *rvc,
-                      const float *acc_in, const float *msgs_in, float *msgs_out, hipStream_t st,
-                      const AccMode &am, bool clear) {
-    const int nch = (ctx->p.M + WAVE - 1) / WAVE;
-    ProfScope prof(ctx, RN_K_BP, n, st);
-    float4 *zero = clear ? reinterpret_cast<float4 *>(am.zero) : nullptr;
-    const int zero4 = zero ? (int)(acc_floats(ctx) / 4) : 0;
-#define RN_BP_(NCH_, STEADY_)                                                                   \
-    hipLaunchKernelGGL((k_bp<NCH_, PACKED, CLIP_IN, STEADY_>), dim3(ray_blocks_mrf(n)),             \
-                       dim3(RAY_BLOCK), 0, st, ctx->p, n, Sv, vox, rvc, acc_in, msgs_in,         \
-                       msgs_out, am.uniform ? 1 : 0, am.bias, am.biased ? 1 : 0, zero, zero4)
-    // the plan path's iterations after the first: everything the kernel would test per chunk
-    // is known here (k_bp's STEADY)
-    const bool steady = PACKED && !CLIP_IN && msgs_in && !am.uniform && am.biased;
-#define RN_BP(NCH_) do { if (steady) RN_BP_(NCH_, true); else RN_BP_(NCH_, false); } while (0)
-    if (nch <= 2) RN_BP(2);
-    else if (nch <= 4) RN_BP(4);
-    else if (nch <= 6) RN_BP(6);
-    else if (nch <= 8) RN_BP(8);
-    else if (nch <= 12) RN_BP(12);
-    else RN_BP(16);
-#undef RN_BP
-#undef RN_BP_
-}
-
-// the scatter kernel for `level` (see launch_bp) over rows [0, n)
-template <bool PACKED>
-void launch_scatter_kernel(rn_ctx *ctx, int n, const float *msgs, const int32_t *vox,
-                           const int32_t *rvc, void *acc_out, hipStream_t st, int level,
-                           bool fixed) {
-    ProfScope prof(ctx, RN_K_SCATTER, n, st);
-    // a work list bound for exactly these rows and this tile shape (else: tiles x box_split)
-    const int32_t *items = PACKED && ctx->sc_items && vox == ctx->sc_vox && n == ctx->sc_rows &&
-                           level == ctx->sc_level ? ctx->sc_items : nullptr;
-#define RN_BOX(RAYS, STEPS, FIXED_, CAP)                                                          \
-    hipLaunchKernelGGL((k_scatter_box<PACKED, RAYS, STEPS, FIXED_>),                              \
-                       items ? dim3(ctx->sc_count, 1) : dim3((n + RAYS - 1) / RAYS, box_split(n, RAYS)), \
-                       dim3(BLOCK), (CAP) * sizeof(double), st, ctx->p, n, msgs, vox, rvc, acc_out, \
-                       ctx->box_stats, CAP,                                                       \
-                       (const int2 *)(PACKED ? slab_boxes_for(ctx, vox, n, true) : nullptr), items)
-#define RN_BOX0_CAP 4096
-    if (level == 0) {
-        if (fixed) RN_BOX(128, 32, true, RN_BOX0_CAP); else RN_BOX(128, 32, false, RN_BOX0_CAP);
-    } else if (level == 1) {
-        if (fixed) RN_BOX(256, 16, true, 6144); else RN_BOX(256, 16, false, 6144);
-    } else if (fixed) {
-        hipLaunchKernelGGL((k_scatter_direct_fixed<PACKED>), dim3(ray_blocks(n)), dim3(BLOCK), 0, st,
-                           ctx->p, n, msgs, vox, rvc, static_cast<unsigned long long *>(acc_out));
-    } else {
-        hipLaunchKernelGGL((k_scatter_slab<PACKED>),
-                           dim3(((n + WAVE - 1) / WAVE) *
-                                ((ctx->p.M + SLAB_STEPS - 1) / SLAB_STEPS)),
-                           dim3(WAVE), 0, st, ctx->p, n, msgs, vox, rvc,
-                           static_cast<float *>(acc_out));
-    }
-#undef RN_BOX
-}
-
-template <bool PACKED, bool CLIP_IN>
-int launch_bp(rn_ctx *ctx, int n, const float *Sv, const int32_t *vox, const int32_t *rvc,
-              const float *acc_in, const float *msgs_in, void *acc_out, float *msgs_out,
-              hipStream_t st, bool patch_rows = false, bool fixed = false,
-              const AccMode &am = AccMode(), bool skip_bp = false) {
-    // Patch-ordered rows start with the LDS-box scatter on 128-ray x 32-step tiles.  The
-    // kernel counts the chunks whose bounding box did not fit its LDS budget; the count of
-    // the previous launches is copied out asynchronously (it may lag a launch) and when too
-    // many overflowed the launcher steps down: more LDS, then narrower chunks, then -- pixel
-    // spacing above the voxel size, nothing to sum per voxel anyway -- the slab scatter.
-    // levels: 0 = 128 x 32 tiles with a 4096-voxel box (32 KB), 1 = 256 x 16 tiles with 6144
-    // voxels (48 KB; measured best of 4096..8192 on the 256^3 grid of config 4), 2 = slab
-    // scatter.  0 -> 1 above 2 % overflowed chunks, 1 -> 2 only above 25 % (the box kernel's
-    // quarter-chunk fallback still beats the slab scatter below that).
-    constexpr int LAST = 2;
-    int level = ctx->scatter_mode == 0 ? LAST : (ctx->scatter_mode == 2 || patch_rows) ? 0 : LAST;
-    if (level == 0) {
-        const unsigned c0 = ctx->box_stats_host[0], c1 = ctx->box_stats_host[1];
-        if (c0 != ctx->box_seen[0] && ctx->box_rebase) {
-            // the counters are cumulative and were last looked at before the reset: what has
-            // arrived mixes launches of the previous scene / tile shape in -- a baseline only
-            ctx->box_seen[0] = c0;
-            ctx->box_seen[1] = c1;
-            ctx->box_rebase = false;
-        } else if (c0 != ctx->box_seen[0]) {   // counters of more launches have arrived
-            ctx->box_obs[0] = c0 - ctx->box_seen[0];
-            ctx->box_obs[1] = c1 - ctx->box_seen[1];
-            ctx->box_seen[0] = c0;
-            ctx->box_seen[1] = c1;
-            const unsigned per = ctx->box_level < LAST - 1 ? 50u : 4u;
-            if (!ctx->box_pin && ctx->box_level < LAST && ctx->box_obs[1] * per > ctx->box_obs[0]) {
-                ctx->box_level++;
-                ctx->box_probe = BOX_PROBE_LAUNCHES;      // look at the new shape as well
-            }
-        }
-        level = ctx->box_level;
-    }
-    // k_bp is bound by VALU issue and its dependent row / gather round trips, the box scatter
-    // by LDS atomics and barriers: with the rows in two halves the scatter of the first half
-    // runs (on the context's second stream) while the second half's messages are computed.
-    const size_t M = (size_t)ctx->p.M, VW = PACKED ? 1 : 3;
-    const bool split = ctx->overlap == 1 || (ctx->overlap == 2 && level >= 1 && level < LAST);
-    const int nA = split && PACKED && n >= 65536 && !skip_bp ? (n / 2 + 255) / 256 * 256 : n;
-    if (!skip_bp) {     // (else: the plane sweep wrote the messages and cleared am.zero)
-        launch_bp_kernel<PACKED, CLIP_IN>(ctx, nA, Sv, vox, rvc, acc_in, msgs_in, msgs_out, st, am, true);
-        RN_LAUNCH_CHECK(ctx);
-    }
-    if (nA < n) {
-        RN_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
-        launch_bp_kernel<PACKED, CLIP_IN>(ctx, n - nA, Sv + nA * M, vox + nA * M * VW, rvc + nA, acc_in,
-                                          msgs_in ? msgs_in + nA * M : nullptr, msgs_out + nA * M, st,
-                                          am, false);
-        RN_LAUNCH_CHECK(ctx);
-        RN_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        launch_scatter_kernel<PACKED>(ctx, nA, msgs_out, vox, rvc, acc_out, ctx->aux, level, fixed);
-        RN_LAUNCH_CHECK(ctx);
-        RN_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-        launch_scatter_kernel<PACKED>(ctx, n - nA, msgs_out + nA * M, vox + nA * M * VW, rvc + nA,
-                                      acc_out, st, level, fixed);
-        RN_LAUNCH_CHECK(ctx);
-        RN_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-    } else {
-        launch_scatter_kernel<PACKED>(ctx, n, msgs_out, vox, rvc, acc_out, st, level, fixed);
-        RN_LAUNCH_CHECK(ctx);
-    }
-    ctx->box_probe_used = true;
-    if (ctx->box_probe > 0) {
-        ctx->box_probe--;
-        if (level < LAST)
-            (void)hipMemcpyAsync(ctx->box_stats_host, ctx->box_stats, 2 * sizeof(unsigned),
-                                 hipMemcpyDeviceToHost, st);
-    }
-    RN_LAUNCH_CHECK(ctx);
-    return RN_OK;
-}
-
-template <bool PACKED, bool CLIP_IN>
-int launch_depth(rn_ctx *ctx, int n, const float *Sv, const int32_t *vox, const int32_t *rvc,
-                 const float *acc, const float *msgs, const float *cc, float *S_new,
-                 float *depth_map, hipStream_t st, int rays_per_center = 0,
-                 const AccMode &am = AccMode(), int cc_stride = 4,
-                 const DepthDest &dest = DepthDest()) {
-    const int nch = (ctx->p.M + WAVE - 1) / WAVE;
-    ProfScope prof(ctx, RN_K_DEPTH, n, st);
-#define RN_DE_(NCH_, STEADY_)                                                                   \
-    hipLaunchKernelGGL((k_depth<NCH_, PACKED, CLIP_IN, STEADY_>), dim3(ray_blocks_mrf(n)),          \
-                       dim3(RAY_BLOCK), 0, st, ctx->p, n, Sv, vox, rvc, acc, msgs, ctx->axes, cc, \
-                       S_new, depth_map, rays_per_center, am.bias, am.biased ? 1 : 0, cc_stride, dest)
-    // (k_depth's STEADY form -- its flags known at compile time, as k_bp's: slower with plain
-    // row loads, 0.746 -> 0.772 ms per step, faster with the non-temporal ones, 0.717 -> 0.699;
-    // -DRN_DEPTH_NO_STEADY: the generic kernel)
-    const bool steady = PACKED && !CLIP_IN && msgs && !S_new && depth_map && am.biased;
-#define RN_DE(NCH_) do { if (steady) RN_DE_(NCH_, true); else RN_DE_(NCH_, false); } while (0)
-    if (nch <= 2) RN_DE(2);
-    else if (nch <= 4) RN_DE(4);
-    else if (nch <= 6) RN_DE(6);
-    else if (nch <= 8) RN_DE(8);
-    else if (nch <= 12) RN_DE(12);
-    else RN_DE(16);
-#undef RN_DE
-#undef RN_DE_
-    RN_LAUNCH_CHECK(ctx);
-    return RN_OK;
-}
-
-inline AccMode uniform_mode(bool uniform) {
-    AccMode am;
-    am.uniform = uniform;
-    return am;
-}
-
-int need_axes(rn_ctx *ctx) {
-    if (!ctx->have_axes)
-        return fail(ctx, RN_ERR_STATE, "rn_set_voxel_grid must be called before this entry point");
-    return RN_OK;
-}
-
-}  // namespace
+// the context and the launchers
+#include "raynet_launch.inl"
 
 extern "C" {
 
@@ -722,11 +273,11 @@ int rn_create(const rn_config *cfg, rn_ctx **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return RN_ERR_NO_DEVICE;
     if (cfg->device < 0 || cfg->device >= ndev) return RN_ERR_NO_DEVICE;
-    if (cfg->M < 1 || cfg->M > 1024 || cfg->D < 2 || cfg->D > 4096 || cfg->N < 2 ||
+    if (cfg->M < 1 || cfg->M > MAX_M || cfg->D < 2 || cfg->D > MAX_D || cfg->N < 2 ||
         cfg->N > MAX_VIEWS || cfg->F < 1 || cfg->H < 1 || cfg->W < 1 || cfg->padding < 0)
         return RN_ERR_INVALID;
     for (int i = 0; i < 3; i++)
-        if (cfg->grid[i] < 1 || cfg->grid[i] > 1024 || !(cfg->bbox[3 + i] > cfg->bbox[i]))
+        if (cfg->grid[i] < 1 || cfg->grid[i] > MAX_GRID_AXIS || !(cfg->bbox[3 + i] > cfg->bbox[i]))
             return RN_ERR_INVALID;
     if ((int64_t)((cfg->grid[0] + 3) / 4) * ((cfg->grid[1] + 3) / 4) * ((cfg->grid[2] + 3) / 4) >=
         ((int64_t)1 << 24))
@@ -734,9 +285,9 @@ int rn_create(const rn_config *cfg, rn_ctx **out) {
     if ((int64_t)(cfg->H + cfg->padding + 1) * (cfg->W + cfg->padding + 1) * cfg->F >=
         ((int64_t)1 << 29))
         return RN_ERR_INVALID;        // feature vectors are addressed with 32-bit byte offsets
+    // (every shape within these limits fits the LDS of a CU: the static_assert at sweep_lds_bytes)
     if (hipSetDevice(cfg->device) != hipSuccess) return RN_ERR_HIP;
     rn_ctx *ctx = new rn_ctx();
-    memset(ctx, 0, sizeof(*ctx));
     ctx->cfg = *cfg;
     Params &p = ctx->p;
     p.M = cfg->M; p.D = cfg->D; p.N = cfg->N; p.F = cfg->F;
@@ -750,18 +301,13 @@ int rn_create(const rn_config *cfg, rn_ctx **out) {
     const char *sm = getenv("RAYNET_HIP_SCATTER_MODE");
     ctx->scatter_mode = sm ? atoi(sm) : -1;
     const char *bs = getenv("RAYNET_HIP_BOX_LEVEL");      // A/B knob: start at this tile shape
-    ctx->box_level = ctx->box_level0 = bs ? max(0, min(2, atoi(bs))) : 0;
-    ctx->box_pin = getenv("RAYNET_HIP_BOX_PIN") != nullptr;
+    ctx->box.start(bs ? max(0, min(BoxPolicy::LAST, atoi(bs))) : 0,
+                   getenv("RAYNET_HIP_BOX_PIN") != nullptr);
     const char *ov = getenv("RAYNET_HIP_OVERLAP");
     ctx->overlap = ov ? (atoi(ov) != 0 ? 1 : 0) : 2;
     ctx->generic_sweep = getenv("RAYNET_HIP_GENERIC_SWEEP") != nullptr;
     const char *rw = getenv("RAYNET_HIP_SWEEP_RAYS_PER_WAVE");
     ctx->sweep_rpw = rw && atoi(rw) == 1 ? 1 : 0;
-    ctx->prof_mask = ~0u;
-    if (sweep_lds(p) > 160 * 1024) {      // before anything is allocated
-        delete ctx;
-        return RN_ERR_INVALID;
-    }
     if (hipMalloc(&ctx->axes, sizeof(float) * (p.gx + p.gy + p.gz)) != hipSuccess ||
         hipMalloc(&ctx->box_stats, 2 * sizeof(unsigned)) != hipSuccess ||
         hipMalloc(&ctx->scalar_dev, sizeof(float)) != hipSuccess ||
@@ -775,7 +321,6 @@ int rn_create(const rn_config *cfg, rn_ctx **out) {
         return RN_ERR_HIP;
     }
     ctx->box_stats_host[0] = ctx->box_stats_host[1] = 0;
-    ctx->box_probe = BOX_PROBE_LAUNCHES;
     *out = ctx;
     return RN_OK;
 }
@@ -802,8 +347,8 @@ void rn_destroy(rn_ctx *ctx) {
 int rn_get_options(const rn_ctx *ctx, rn_options *out) {
     if (!ctx || !out) return RN_ERR_INVALID;
     out->scatter_mode = ctx->scatter_mode;
-    out->box_level = ctx->box_level0;
-    out->box_pin = ctx->box_pin ? 1 : 0;
+    out->box_level = ctx->box.level0;
+    out->box_pin = ctx->box.pin ? 1 : 0;
     out->overlap = ctx->overlap;
     out->generic_sweep = ctx->generic_sweep;
     out->sweep_rays_per_wave = ctx->sweep_rpw;
@@ -817,14 +362,10 @@ int rn_set_options(rn_ctx *ctx, const rn_options *opt) {
         (opt->sweep_rays_per_wave != 0 && opt->sweep_rays_per_wave != 1))
         return fail(ctx, RN_ERR_INVALID, "rn_set_options: value out of range");
     ctx->scatter_mode = opt->scatter_mode;
-    ctx->box_level = ctx->box_level0 = opt->box_level;
-    ctx->box_pin = opt->box_pin != 0;
+    ctx->box.start(opt->box_level, opt->box_pin != 0);
     ctx->overlap = opt->overlap;
     ctx->generic_sweep = opt->generic_sweep != 0;
     ctx->sweep_rpw = opt->sweep_rays_per_wave;
-    ctx->box_obs[0] = ctx->box_obs[1] = 0;
-    ctx->box_probe = BOX_PROBE_LAUNCHES;
-    ctx->box_rebase = ctx->box_probe_used;
     return RN_OK;
 }
 
@@ -859,10 +400,7 @@ int rn_fill_i32(rn_ctx *ctx, int32_t *dst, int64_t count, int32_t value, void *s
 
 int rn_sample_rays(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *P_inv,
                    const float *camera_center, float *ray_start, float *ray_end, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !P_inv || !camera_center || !ray_start || !ray_end)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(ray_idxs, P_inv, camera_center, ray_start, ray_end));
     hipLaunchKernelGGL(k_sample_rays, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), ctx->p, n,
                        ray_idxs, P_inv, camera_center, ray_start, ray_end);
     RN_LAUNCH_CHECK(ctx);
@@ -871,10 +409,7 @@ int rn_sample_rays(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float 
 
 int rn_sample_points(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *P_inv,
                      const float *camera_center, float *points, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !P_inv || !camera_center || !points)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(ray_idxs, P_inv, camera_center, points));
     hipLaunchKernelGGL(k_sample_points, dim3(ray_blocks(n)), dim3(BLOCK), 0, S(stream), ctx->p, n,
                        ray_idxs, P_inv, camera_center, points);
     RN_LAUNCH_CHECK(ctx);
@@ -884,10 +419,7 @@ int rn_sample_points(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const floa
 int rn_compute_similarities(rn_ctx *ctx, int32_t n, const float *features, const float *P,
                             const float *ray_start, const float *ray_end, float *Sp,
                             void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !features || !P || !ray_start || !ray_end || !Sp)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(features, P, ray_start, ray_end, Sp));
     SweepArgs a{n, nullptr, stacked_views(ctx->p, features), P, nullptr, nullptr, ray_start,
                 ray_end, nullptr, nullptr, nullptr, Sp, nullptr, nullptr, nullptr};
     launch_sweep<0, false>(ctx, a, true, S(stream));
@@ -897,10 +429,7 @@ int rn_compute_similarities(rn_ctx *ctx, int32_t n, const float *features, const
 
 int rn_voxel_traversal(rn_ctx *ctx, int32_t n, const float *ray_start, const float *ray_end,
                        int32_t *rvi, int32_t *rvc, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_start || !ray_end || !rvi || !rvc)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(ray_start, ray_end, rvi, rvc));
     {
         ProfScope prof(ctx, RN_K_TRAVERSE, n, S(stream));
         hipLaunchKernelGGL((k_traverse<false>), dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, S(stream),
@@ -915,12 +444,9 @@ int rn_voxel_traversal(rn_ctx *ctx, int32_t n, const float *ray_start, const flo
 int rn_planes_to_voxels(rn_ctx *ctx, int32_t n, const int32_t *rvi, const int32_t *rvc,
                         const float *ray_start, const float *ray_end, const float *Sp,
                         float *S_new, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !rvi || !rvc || !ray_start || !ray_end || !Sp || !S_new)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(rvi, rvc, ray_start, ray_end, Sp, S_new));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     SweepArgs a{n, nullptr, FeatureViews{}, nullptr, nullptr, nullptr, ray_start, ray_end, Sp,
                 rvi, rvc, nullptr, S_new, nullptr, nullptr};
     launch_sweep<1, false>(ctx, a, false, S(stream));
@@ -931,10 +457,7 @@ int rn_planes_to_voxels(rn_ctx *ctx, int32_t n, const int32_t *rvi, const int32_
 int rn_bp_sweep(rn_ctx *ctx, int32_t n, const float *Sv, const int32_t *rvi, const int32_t *rvc,
                 const float *acc_in, const float *msgs_in, float *acc_out, float *msgs_out,
                 void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !Sv || !rvi || !rvc || !acc_in || !acc_out || !msgs_out)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");   /* msgs_in == NULL: all-zero messages */
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(Sv, rvi, rvc, acc_in, acc_out, msgs_out));   /* msgs_in == NULL: all-zero messages */
     return launch_bp<false, true>(ctx, n, Sv, rvi, rvc, acc_in, msgs_in, acc_out, msgs_out,
                                   S(stream));
 }
@@ -942,10 +465,7 @@ int rn_bp_sweep(rn_ctx *ctx, int32_t n, const float *Sv, const int32_t *rvi, con
 int rn_depth_estimation(rn_ctx *ctx, int32_t n, const float *Sv, const int32_t *rvi,
                         const int32_t *rvc, const float *acc, const float *msgs, float *S_new,
                         void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !Sv || !rvi || !rvc || !acc || !msgs || !S_new)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(Sv, rvi, rvc, acc, msgs, S_new));
     return launch_depth<false, true>(ctx, n, Sv, rvi, rvc, acc, msgs, nullptr, S_new, nullptr,
                                      S(stream));
 }
@@ -953,10 +473,7 @@ int rn_depth_estimation(rn_ctx *ctx, int32_t n, const float *Sv, const int32_t *
 int rn_mvcnn_similarities(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *features,
                           const float *P, const float *P_inv, const float *camera_center,
                           float *Sp, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features || !P || !P_inv || !camera_center || !Sp)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, Sp));
     SweepArgs a{n, ray_idxs, stacked_views(ctx->p, features), P, P_inv, camera_center, nullptr,
                 nullptr, nullptr, nullptr, nullptr, Sp, nullptr, nullptr, nullptr};
     launch_sweep<0, false>(ctx, a, true, S(stream));
@@ -967,11 +484,7 @@ int rn_mvcnn_similarities(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const
 int rn_mvcnn_depth(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *features,
                    const float *P, const float *P_inv, const float *camera_center, float *Sp,
                    float *points, float *depth_map, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features || !P || !P_inv || !camera_center || !Sp ||
-        !points || !depth_map)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, Sp, points, depth_map));
     SweepArgs a{n, ray_idxs, stacked_views(ctx->p, features), P, P_inv, camera_center, nullptr,
                 nullptr, nullptr, nullptr, nullptr, Sp, nullptr, depth_map, points};
     launch_sweep<0, false>(ctx, a, true, S(stream));
@@ -1000,13 +513,9 @@ static int prefix_api(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const flo
 int rn_mvcnn_voxel_space(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *features,
                          const float *P, const float *P_inv, const float *camera_center,
                          int32_t *rvi, int32_t *rvc, float *S_voxel, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features || !P || !P_inv || !camera_center || !rvi ||
-        !rvc || !S_voxel)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     return prefix_api(ctx, n, ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel,
                       S(stream));
 }
@@ -1030,13 +539,10 @@ int rn_fused_bp_sweep(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const flo
                       const float *P, const float *P_inv, const float *camera_center,
                       int32_t *rvi, int32_t *rvc, float *S_voxel, const float *acc_in,
                       const float *msgs_in, float *acc_out, float *msgs_out, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features || !P || !P_inv || !camera_center || !rvi ||
-        !rvc || !S_voxel || !acc_in || !msgs_in || !acc_out || !msgs_out)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel, acc_in,
+                            msgs_in, acc_out, msgs_out));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     rc = prefix_api(ctx, n, ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel,
                     S(stream));
     if (rc) return rc;
@@ -1048,13 +554,10 @@ int rn_fused_depth(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float 
                    const float *P, const float *P_inv, const float *camera_center, int32_t *rvi,
                    int32_t *rvc, float *S_voxel, const float *acc, const float *msgs,
                    float *depth_map, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features || !P || !P_inv || !camera_center || !rvi ||
-        !rvc || !S_voxel || !acc || !msgs || !depth_map)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel, acc,
+                            msgs, depth_map));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     rc = prefix_api(ctx, n, ray_idxs, features, P, P_inv, camera_center, rvi, rvc, S_voxel,
                     S(stream));
     if (rc) return rc;
@@ -1068,18 +571,12 @@ int rn_acc_copies(const rn_ctx *ctx) { return ctx ? 1 : 0; }
 
 int rn_scatter_reset(rn_ctx *ctx) {
     if (!ctx) return RN_ERR_INVALID;
-    ctx->box_level = ctx->box_level0;
-    ctx->box_obs[0] = ctx->box_obs[1] = 0;
-    ctx->box_probe = BOX_PROBE_LAUNCHES;
-    // launches since the last look at the (cumulative) counters belong to the old scene
-    ctx->box_rebase = ctx->box_probe_used;
+    ctx->box.reset();
     return RN_OK;
 }
 
 int rn_scatter_settled(const rn_ctx *ctx) {
-    // no scatter launch copies its overflow counters out any more: the tile shape stays as it is
-    // until the next rn_scatter_reset / rn_set_options (what a captured step relies on)
-    return ctx && ctx->box_probe == 0 ? 1 : 0;
+    return ctx && ctx->box.settled() ? 1 : 0;
 }
 
 int64_t rn_slab_boxes_size(const rn_ctx *ctx, int64_t rows) {
@@ -1114,9 +611,7 @@ int rn_scene_bind_scatter_items(rn_ctx *ctx, const int32_t *vox, int64_t rows, i
 
 int rn_scatter_state(const rn_ctx *ctx, int32_t *level, uint32_t *chunks, uint32_t *overflowed) {
     if (!ctx || !level || !chunks || !overflowed) return RN_ERR_INVALID;
-    *level = ctx->box_level;
-    *chunks = ctx->box_obs[0];
-    *overflowed = ctx->box_obs[1];
+    ctx->box.state(level, chunks, overflowed);
     return RN_OK;
 }
 
@@ -1169,13 +664,9 @@ int rn_scene_prepare(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs,
                      const float *const *features_views_host, const float *P, const float *P_inv,
                      const float *camera_center, const int32_t *order, int32_t *vox, int32_t *rvc,
                      float *Sr, float *ray_segments, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !ray_idxs || !features_views_host || !P || !P_inv || !camera_center ||
-        !vox || !rvc || !Sr)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(ray_idxs, features_views_host, P, P_inv, camera_center, vox, rvc, Sr));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     if (ctx->sb_boxes && vox >= ctx->sb_vox && vox < ctx->sb_vox + ctx->sb_rows * (int64_t)ctx->p.M)
         ctx->sb_valid_lo = ctx->sb_valid_hi = 0;      // this entry does not maintain slab boxes
     FeatureViews fv;
@@ -1199,14 +690,6 @@ int rn_scene_prepare(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs,
 }
 
 }  // extern "C"
-
-namespace {
-// LDS a workgroup of the plane sweep may take and still leave room for RN_SWEEP_MIN_WAVES
-// wavefronts per SIMD (4 per workgroup, 160 KB per CU)
-inline bool fold_fits(const Params &p) {
-    return sweep_lds(p, 3) <= (size_t)160 * 1024 / ((RN_SWEEP_MIN_WAVES * 4 + SWEEP_WAVES - 1) / SWEEP_WAVES);
-}
-}  // namespace
 
 // rn_scene_prepare_all; with msgs_fold the plane sweep also writes BP iteration 0's messages
 // (k_sweep_map MAPMODE 3, first_sweep_messages)
@@ -1238,7 +721,6 @@ static int scene_prepare_all_impl(rn_ctx *ctx, int32_t n_images, int32_t n, int6
         return fail(ctx, RN_ERR_INVALID, "bad argument");
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     const int N = ctx->p.N;
     const int cam_stride = 12 * N + 12 + 4;
     const size_t M = (size_t)ctx->p.M;
@@ -1293,7 +775,7 @@ static int scene_prepare_all_impl(rn_ctx *ctx, int32_t n_images, int32_t n, int6
             launch_sweep<2, true>(ctx, a, true, st);
         }
     };
-    const bool split = ctx->overlap == 1 || (ctx->overlap == 2 && ctx->box_level == 1);
+    const bool split = ctx->overlap == 1 || (ctx->overlap == 2 && ctx->box.level == 1);
     const int gA = split && n_images >= 2 && (int64_t)n * n_images >= 65536
                        ? (n_images + 1) / 2 : n_images;
     if (gA < n_images) {
@@ -1349,10 +831,7 @@ int rn_scene_count_voxels(rn_ctx *ctx, int32_t n_images, int32_t n, const int32_
 int rn_scene_bp_sweep(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
                       const int32_t *rvc, const float *acc_in, float *msgs, float *acc_part,
                       int32_t first_sweep, int32_t row_layout, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !Sr || !vox || !rvc || !acc_in || !msgs || !acc_part)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
-    if (n == 0) return RN_OK;
+    RN_OPEN(ctx, n, all_set(Sr, vox, rvc, acc_in, msgs, acc_part));
     return launch_bp<true, false>(ctx, n, Sr, vox, rvc, acc_in,
                                   (first_sweep & RN_SWEEP_ZERO_MSGS) ? nullptr : msgs, acc_part,
                                   msgs, S(stream), row_layout == RN_ROWS_PATCHES, false,
@@ -1363,9 +842,7 @@ int rn_scene_bp_sweep_fixed(rn_ctx *ctx, int32_t n, const float *Sr, const int32
                             const int32_t *rvc, const float *acc_in, float *msgs,
                             int64_t *acc_part_fixed, int32_t first_sweep, int32_t row_layout,
                             void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !Sr || !vox || !rvc || !acc_in || !msgs || !acc_part_fixed)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, vox, rvc, acc_in, msgs, acc_part_fixed));
     return launch_bp<true, false>(ctx, n, Sr, vox, rvc, acc_in,
                                   (first_sweep & RN_SWEEP_ZERO_MSGS) ? nullptr : msgs,
                                   acc_part_fixed, msgs, S(stream), row_layout == RN_ROWS_PATCHES,
@@ -1428,13 +905,10 @@ int rn_scene_depth(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
                    const int32_t *rvc, const float *acc, const float *msgs,
                    const float *camera_center, int32_t rays_per_center, float *S_new,
                    float *depth_map, void *stream) {
-    if (ctx && n == 0) return RN_OK;   /* empty launch: pointers may be null */
-    if (!ctx || n < 0 || !Sr || !vox || !rvc || !acc || !msgs || (!S_new && !depth_map) ||
-        (depth_map && !camera_center))
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, vox, rvc, acc, msgs) && (S_new || depth_map) &&
+                        (!depth_map || camera_center));
     int rc = need_axes(ctx);
     if (rc) return rc;
-    if (n == 0) return RN_OK;
     if (rays_per_center < 0) return fail(ctx, RN_ERR_INVALID, "bad argument");
     return launch_depth<true, false>(ctx, n, Sr, vox, rvc, acc, msgs, camera_center, S_new,
                                      depth_map, S(stream), rays_per_center);
@@ -1587,8 +1061,7 @@ int rn_prof_end(rn_ctx *ctx, int32_t *count, int32_t *kernel_ids_host, int32_t *
 }
 
 int rn_selftest_arith(rn_ctx *ctx, int32_t n, const float *a, float *out, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !a || !out) return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(a, out));
     hipLaunchKernelGGL(k_selftest_arith, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, a, out);
     RN_LAUNCH_CHECK(ctx);
     return RN_OK;
@@ -1596,8 +1069,7 @@ int rn_selftest_arith(rn_ctx *ctx, int32_t n, const float *a, float *out, void *
 
 int rn_selftest_quotient(rn_ctx *ctx, int32_t n, const float *x, const float *d, float *out,
                          void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !x || !d || !out) return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(x, d, out));
     hipLaunchKernelGGL(k_selftest_quotient, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, x,
                        d, out);
     RN_LAUNCH_CHECK(ctx);
@@ -1606,9 +1078,7 @@ int rn_selftest_quotient(rn_ctx *ctx, int32_t n, const float *x, const float *d,
 
 int rn_selftest_feature_offsets(rn_ctx *ctx, int32_t n, const float *P, const float *ray_start,
                                 const float *ray_end, int32_t *out, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !P || !ray_start || !ray_end || !out)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(P, ray_start, ray_end, out));
     hipLaunchKernelGGL(k_selftest_offsets, dim3(ray_blocks(n)), dim3(BLOCK), 0, S(stream), ctx->p, n,
                        P, ray_start, ray_end, out);
     RN_LAUNCH_CHECK(ctx);
@@ -1617,8 +1087,7 @@ int rn_selftest_feature_offsets(rn_ctx *ctx, int32_t n, const float *P, const fl
 
 int rn_selftest_mapping(rn_ctx *ctx, int32_t n, const float *a, const float *b, const float *t,
                         float *out, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !a || !b || !t || !out) return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(a, b, t, out));
     hipLaunchKernelGGL(k_selftest_mapping, dim3(thread_blocks(n)), dim3(BLOCK),
                        sizeof(float) * (ctx->p.D + 1), S(stream), ctx->p, n, a, b, t, out);
     RN_LAUNCH_CHECK(ctx);

@@ -425,9 +425,7 @@ int rn_mesh_build(rn_ctx *ctx, int32_t n, const float *triangles, const int64_t 
 int rn_mesh_raycast(rn_ctx *ctx, int32_t n, const float *origins, const float *destinations,
                     const float *nodes, const float *leaves, float *points, int32_t *tri,
                     void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !origins || !destinations || !nodes || !leaves || !points || !tri)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(origins, destinations, nodes, leaves, points, tri));
     hipLaunchKernelGGL(k_mesh_raycast, dim3((n + MESH_RAY_BLOCK - 1) / MESH_RAY_BLOCK),
                        dim3(MESH_RAY_BLOCK), 0, S(stream), n, origins, destinations,
                        reinterpret_cast<const MeshNode *>(nodes),

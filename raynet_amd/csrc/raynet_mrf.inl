@@ -68,10 +68,10 @@ __device__ __forceinline__ float gather_acc(const float *__restrict__ acc, int l
 // kernel arguments in one scalar fetch up front -- no gain, the limit was never the dependent
 // round trips (profiles/r02_exp_wave_startup.txt).  What did help is not reading gridDim /
 // blockDim at all: ray_of_wave.)
-#define RN_BP_NT true
-#define RN_DEPTH_NT true
+// non-temporal row loads / stores of k_bp and k_depth
+constexpr bool BP_NT = true, DEPTH_NT = true;
 // bodies of up to this many chunks issue all their accumulator gathers back to back (bp_ray)
-#define RN_GATHER_BATCH_MAX 6
+constexpr int GATHER_BATCH_MAX = 6;
 template <int NCH>
 struct RayRows {
     float sv[NCH], mv[NCH];
@@ -107,7 +107,7 @@ __device__ __forceinline__ void load_rows(const Params &p, RayRows<NCH> &R,
     // the voxel words first, for all chunks: the accumulator gathers depend on them and on
     // nothing else, and loads return in the order they were issued -- the columns and messages
     // are still in flight while the gathers go out
-    constexpr bool VOX_FIRST = NCH <= RN_GATHER_BATCH_MAX;
+    constexpr bool VOX_FIRST = NCH <= GATHER_BATCH_MAX;
 #pragma unroll
     for (int ch = 0; ch < (VOX_FIRST ? NCH : 0); ch++) {
         const int i = ch * WAVE + lane;
@@ -181,7 +181,7 @@ __device__ __forceinline__ void bp_ray(const Params &p, int r, int count, int la
         biased = true;
     }
     RayRows<NB> cur;
-    load_rows<NB, PACKED, RN_BP_NT, STEADY>(p, cur, S, vox, msgs_in, r, count, lane, !uniform_acc);
+    load_rows<NB, PACKED, BP_NT, STEADY>(p, cur, S, vox, msgs_in, r, count, lane, !uniform_acc);
     // accumulator gather (depends on the voxel rows).  uniform_acc: every voxel holds
     // acc_in[0] (the first iteration starts from the prior everywhere) -- nothing to gather,
     // and with zero messages on top the occupancy is one constant for the whole sweep.
@@ -195,10 +195,10 @@ __device__ __forceinline__ void bp_ray(const Params &p, int r, int count, int la
         // the lanes are masked where the value would be used.  (Guarded per chunk, every
         // gather sat in its own block with the addition that uses it and the wavefront paid
         // NB dependent round trips in a row.)
-        // (Bodies of more than RN_GATHER_BATCH_MAX chunks -- config 4's M = 768 -- keep the
+        // (Bodies of more than GATHER_BATCH_MAX chunks -- config 4's M = 768 -- keep the
         // guarded form: twelve gathers at once into a 67 MB accumulator were measured slower,
         // k_bp 9.42 -> 9.80 ms per step there against 1.571 -> 1.515 at config 2.)
-        if (NB <= RN_GATHER_BATCH_MAX) {
+        if (NB <= GATHER_BATCH_MAX) {
 #pragma unroll
             for (int ch = 0; ch < NB; ch++) av[ch] = gather_acc(acc_in, lin_of<PACKED>(p, cur.pk[ch]));
             // acc_in holds the messages' SUM only and the prior is added here (the same
@@ -287,7 +287,7 @@ __device__ __forceinline__ void bp_ray(const Params &p, int r, int count, int la
                 const float pos = cex[ch] + tsv[ch];
                 const float neg = cex[ch] + bp_div(suf[ch], 1.0f - ov[ch]);
                 const float m = bp_log_ratio(pos, neg);
-                row_store<RN_BP_NT>(mout_row, (unsigned)i, m);
+                row_store<BP_NT>(mout_row, (unsigned)i, m);
             }
         }
     }
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_bp(Params p, int n, const float *
         for (int i = w * WAVE + (int)(threadIdx.x & (WAVE - 1)); i < zero_count4; i += nw * WAVE)
             zero_buf[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const int r = ray_of_wave<RAY_BLOCK, RN_XCD_CHUNK_BP>(n, lane);
+    const int r = ray_of_wave<RAY_BLOCK, XCD_CHUNK_BP>(n, lane);
     if (r < 0) return;
     const int count = min(uniform(rvc[r]), p.M);
     if (count <= 1) return;   // mrf_np.py:300: such rays send nothing
@@ -332,11 +332,10 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_bp(Params p, int n, const float *
 // plane through the camera, so inside one slab of the dominant axis their voxels share
 // (nearly) the same column of the grid and differ along z -- consecutive floats.  One
 // instruction then touches a handful of cache lines instead of 64 (an L2 float atomic
-// costs one request per line: 21 G/s scattered vs 324 G/s coalesced, tools/atomic_bench.hip).
+// costs one request per line: 21 G/s scattered vs 324 G/s coalesced, profiles/r01_atomic_microbench.txt).
 // Any ray order is CORRECT (every element is emitted exactly once; the flush loop takes
 // what an unexpected ordering left behind); coherence only buys speed.
-#define RN_SLAB_STEPS 32
-constexpr int SLAB_STEPS = RN_SLAB_STEPS;     // steps of a tile: 16, 32 or 64
+constexpr int SLAB_STEPS = 32;     // steps of a tile: 16, 32 or 64
 constexpr int SLAB_PAD = SLAB_STEPS + 1;
 template <bool PACKED>
 __global__ __launch_bounds__(WAVE) void k_scatter_slab(Params p, int n,
@@ -467,7 +466,7 @@ __global__ __launch_bounds__(WAVE) void k_scatter_slab(Params p, int n,
                 if (__ballot(emit) == 0) break;
                 // Neighbouring rays usually sit in the SAME voxel (ray spacing < voxel size);
                 // an instruction with duplicate addresses is serialised by the L2 (x6 for
-                // pairs, tools/atomic_bench2.hip).  Runs of equal addresses in adjacent lanes
+                // pairs, profiles/r01_atomic_microbench2_address_patterns.txt).  Runs of equal addresses in adjacent lanes
                 // are therefore summed first (segmented scan inside rows of 16 lanes) and only
                 // the last lane of each run issues the atomic.
                 float val = 0.0f;
@@ -504,7 +503,7 @@ __global__ __launch_bounds__(WAVE) void k_scatter_slab(Params p, int n,
 // A tile of BOX_RAYS neighbouring rays x BOX_STEPS steps covers a compact block of the grid
 // in which every voxel is hit by ~10-20 of the tile's rays (ray spacing << voxel size).
 // The tile's messages are therefore summed in a dense LDS image of their bounding box
-// in DOUBLE (measured, tools/lds_atomic_bench.hip: ds_add_f64 runs at ~1.7 T lane-ops/s,
+// in DOUBLE (measured, profiles/r01_lds_atomic_microbench.txt: ds_add_f64 runs at ~1.7 T lane-ops/s,
 // ds_add_f32 at 0.2 T/s whatever the addresses; the sums also become order-independent to
 // ~1e-16, i.e. the accumulator is reproducible run to run) and the box is flushed once, so
 // there is one global atomic per DISTINCT voxel of the tile instead of one per (ray, voxel).
@@ -581,13 +580,13 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_box(Params p, int n,
     // Without a list: grid.x = tiles, grid.y workgroups share a tile taking every grid.y-th chunk.
     int r0, chunk0 = (int)blockIdx.y, chunk_step = (int)gridDim.y, chunk_end = 1 << 20;
     if (items) {
-        const int item = items[xcd_block<RN_XCD_CHUNK_SCATTER>(blockIdx.x, gridDim.x)];
+        const int item = items[xcd_block<XCD_CHUNK_SCATTER>(blockIdx.x, gridDim.x)];
         r0 = (item >> 12) * BOX_RAYS;
         chunk0 = (item >> 6) & 63;
         chunk_end = chunk0 + (item & 63);
         chunk_step = 1;
     } else {
-        r0 = xcd_block<RN_XCD_CHUNK_SCATTER>(blockIdx.x, gridDim.x) * BOX_RAYS;
+        r0 = xcd_block<XCD_CHUNK_SCATTER>(blockIdx.x, gridDim.x) * BOX_RAYS;
     }
     // a wavefront instruction covers RPI rays x BOX_STEPS steps; thread (sub, col) of wave w
     // owns step col of the rays w*RPI + sub + k*STRIDE
@@ -885,10 +884,10 @@ __device__ __forceinline__ void depth_ray(const Params &p, int r, int count, int
     }
     RayRows<NB> cur;
     // (rows streamed once, like k_bp's: non-temporal, out of the L2 ways the gathers live in --
-    // k_depth 0.742 -> 0.715 ms per step; -DRN_DEPTH_NT=false: plain loads)
-    load_rows<NB, PACKED, RN_DEPTH_NT, STEADY>(p, cur, S, vox, msgs, r, count, lane);
+    // k_depth 0.742 -> 0.715 ms per step against plain loads)
+    load_rows<NB, PACKED, DEPTH_NT, STEADY>(p, cur, S, vox, msgs, r, count, lane);
     float av[NB];
-    if (NB <= RN_GATHER_BATCH_MAX) {
+    if (NB <= GATHER_BATCH_MAX) {
         // (all gathers back to back, entries beyond the count gather entry 0: see bp_ray)
 #pragma unroll
         for (int ch = 0; ch < NB; ch++) av[ch] = gather_acc(acc, lin_of<PACKED>(p, cur.pk[ch]));
@@ -960,7 +959,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_depth(Params p, int n, const floa
                                                  float acc_bias, int biased, int cc_stride,
                                                  DepthDest dest) {
     int lane;
-    const int r = ray_of_wave<RAY_BLOCK, RN_XCD_CHUNK_DEPTH>(n, lane);
+    const int r = ray_of_wave<RAY_BLOCK, XCD_CHUNK_DEPTH>(n, lane);
     if (r < 0) return;
     const int group = rays_per_center > 0 ? r / rays_per_center : 0;
     if (rays_per_center > 0 && cc) cc += (size_t)cc_stride * group;

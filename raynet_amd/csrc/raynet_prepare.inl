@@ -44,8 +44,7 @@ __global__ void k_first_occupancy(float prior, float *out) { out[0] = occupancy_
 // [64 rays][TRAV_TILE steps] in LDS and writes finished tiles as coalesced row segments
 // (16 steps: 0.42 ms per scene against 0.46 at 32 and 0.70 at 64 -- the tile's LDS decides how
 // many of these serial, latency-bound threads a CU holds).
-#define RN_TRAV_TILE 16
-constexpr int TRAV_TILE = RN_TRAV_TILE;     // steps collected per flush (the packed list's slab boxes are per 16-step tile: k_traverse<true> needs 16; 32 / 64 compile for the reference layout only)
+constexpr int TRAV_TILE = 16;     // steps collected per flush (the packed list's slab boxes are per 16-step tile: k_traverse<true> needs 16; 32 / 64 compile for the reference layout only)
 template <bool PACKED>
 __global__ __launch_bounds__(WAVE) void k_traverse(Params p, int n,
                                                    const int32_t *__restrict__ ray_idxs,
@@ -264,8 +263,8 @@ __global__ __launch_bounds__(WAVE) void k_traverse(Params p, int n,
 // and the 4-view sweep (which would spill) are left alone
 // cache policy of the list's LDS-DMA loads: 2 = non-temporal (read once here; k_sweep_map 2.957 -> 2.904 ms
 // with it: the feature gathers keep the L2), 0 = default
-#define RN_SWEEP_LIST_CPOL 2
-#define RN_SWEEP_MIN_WAVES 6
+constexpr int SWEEP_LIST_CPOL = 2;
+constexpr int SWEEP_MIN_WAVES = 6;
 // BP iteration 0 of one ray straight from its clipped + renormalised column, which the plane
 // sweep still holds in LDS when it stores it (mrf_bp.cu:88-177 with the prior in every voxel and
 // no messages yet: ONE occupancy for the whole ray, nothing to gather, nothing to read) -- the
@@ -464,12 +463,12 @@ __device__ __forceinline__ int stage_voxel_row(const Params &p, const int32_t *_
     typedef __attribute__((address_space(3))) void *lptr;
     for (int c = 0; c < count; c += WAVE)
         if (c + lane < p.M)
-            __builtin_amdgcn_global_load_lds((gptr)(vrow + c + lane), (lptr)(vals + c), 4, 0, RN_SWEEP_LIST_CPOL);
+            __builtin_amdgcn_global_load_lds((gptr)(vrow + c + lane), (lptr)(vals + c), 4, 0, SWEEP_LIST_CPOL);
     return (count + WAVE - 1) & ~(WAVE - 1);
 }
 
 template <int SIM, int NV, int LPS, int MAPMODE, bool PACKED>
-__global__ __launch_bounds__(SWEEP_BLOCK, (SIM == 2 && MAPMODE >= 2 && NV >= 5 && NV <= SWEEP_UNROLL2_MAX_VIEWS ? RN_SWEEP_MIN_WAVES : 1))
+__global__ __launch_bounds__(SWEEP_BLOCK, (SIM == 2 && MAPMODE >= 2 && NV >= 5 && NV <= SWEEP_UNROLL2_MAX_VIEWS ? SWEEP_MIN_WAVES : 1))
 void k_sweep_map(
     Params p, int n, const int32_t *__restrict__ ray_idxs, FeatureViews fv,
     const float *__restrict__ P, const float *__restrict__ P_inv, const float *__restrict__ cc,
@@ -517,7 +516,7 @@ void k_sweep_map(
         __syncthreads();
     }
     int lane;
-    int r = ray_of_wave<SWEEP_BLOCK, RN_XCD_CHUNK_SWEEP>(n, lane, xcd_chunk);
+    int r = ray_of_wave<SWEEP_BLOCK, XCD_CHUNK_SWEEP>(n, lane, xcd_chunk);
     if (r < 0) return;
     if (order) r = uniform(order[r]);      // schedule only: which ray this wavefront takes
 
@@ -626,7 +625,7 @@ void k_sweep_map_packed(
         __syncthreads();
     }
     int lane;
-    const int w = ray_of_wave<SWEEP_BLOCK, RN_XCD_CHUNK_SWEEP>(nwaves, lane, xcd_chunk);
+    const int w = ray_of_wave<SWEEP_BLOCK, XCD_CHUNK_SWEEP>(nwaves, lane, xcd_chunk);
     if (w < 0) return;
     const int r0 = w * RPW;
     const int nrays = min(RPW, n - r0);

@@ -239,9 +239,7 @@ extern "C" {
 int rn_train_bp_sweep(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *rvi,
                       const int32_t *rvc, const float *acc_in, const float *msgs_in,
                       float *acc_out, float *msgs_out, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !Sr || !rvi || !rvc || !acc_in || !acc_out || !msgs_out)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, rvi, rvc, acc_in, acc_out, msgs_out));
     return launch_bp<false, false>(ctx, n, Sr, rvi, rvc, acc_in, msgs_in, acc_out, msgs_out,
                                    S(stream));
 }
@@ -249,9 +247,7 @@ int rn_train_bp_sweep(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *rv
 int rn_train_depth(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *rvi,
                    const int32_t *rvc, const float *acc, const float *msgs, float *S_new,
                    void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !Sr || !rvi || !rvc || !acc || !msgs || !S_new)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, rvi, rvc, acc, msgs, S_new));
     return launch_depth<false, false>(ctx, n, Sr, rvi, rvc, acc, msgs, nullptr, S_new, nullptr,
                                       S(stream));
 }
@@ -260,10 +256,7 @@ int rn_train_bp_sweep_bwd(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t
                           const int32_t *rvc, const float *acc_in, const float *msgs_in,
                           const float *g_msgs_out, const float *g_acc_out, float *g_Sr,
                           float *g_acc_in, float *g_msgs_in, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !Sr || !rvi || !rvc || !acc_in || !msgs_in || !g_msgs_out || !g_Sr ||
-        !g_acc_in || !g_msgs_in)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, rvi, rvc, acc_in, msgs_in, g_msgs_out, g_Sr, g_acc_in, g_msgs_in));
     const size_t lds = sizeof(float) * TRAIN_ROWS * ctx->p.M;
     if (lds > 64 * 1024) return fail(ctx, RN_ERR_INVALID, "M > 1170 not supported by the training kernels");
     hipLaunchKernelGGL((k_ray_bwd<0, false>), dim3(n), dim3(WAVE), lds, S(stream), ctx->p, n, Sr, rvi,
@@ -276,10 +269,7 @@ int rn_train_depth_bwd(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *r
                        const int32_t *rvc, const float *acc, const float *msgs,
                        const float *g_S_new, float *g_Sr, float *g_acc, float *g_msgs,
                        void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !Sr || !rvi || !rvc || !acc || !msgs || !g_S_new || !g_Sr || !g_acc ||
-        !g_msgs)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(Sr, rvi, rvc, acc, msgs, g_S_new, g_Sr, g_acc, g_msgs));
     const size_t lds = sizeof(float) * TRAIN_ROWS * ctx->p.M;
     if (lds > 64 * 1024) return fail(ctx, RN_ERR_INVALID, "M > 1170 not supported by the training kernels");
     hipLaunchKernelGGL((k_ray_bwd<1, false>), dim3(n), dim3(WAVE), lds, S(stream), ctx->p, n, Sr, rvi,
@@ -291,9 +281,7 @@ int rn_train_depth_bwd(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *r
 int rn_plane_weights(rn_ctx *ctx, int32_t n, const int32_t *rvi, const int32_t *rvc,
                      const float *ray_start, const float *ray_end, int32_t *left, float *c1,
                      float *c2, void *stream) {
-    if (ctx && n == 0) return RN_OK;
-    if (!ctx || n < 0 || !rvi || !rvc || !ray_start || !ray_end || !left || !c1 || !c2)
-        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    RN_OPEN(ctx, n, all_set(rvi, rvc, ray_start, ray_end, left, c1, c2));
     int rc = need_axes(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL((k_plane_weights<false>), dim3(ray_blocks(n)), dim3(BLOCK), 0, S(stream),

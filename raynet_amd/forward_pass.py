@@ -962,10 +962,9 @@ class RayNetForwardPass(ForwardPass):
                 ctx.bind_scatter_items(None)
             return
         if plan.get("items_level") != level:
-            import os
             plan["items"] = ctx.bind_scatter_items(
                 plan["vox"], plan["rvc"], level,
-                target_items=int(os.environ.get("RAYNET_SCATTER_TARGET", "2048")))    # (A/B knob; profiles/r04_exp_scatter_items.txt)
+                target_items=2048)      # (best of the A/B in profiles/r04_exp_scatter_items.txt)
             plan["items_level"] = level
             plan["graphs"] = {}                  # (a captured step has the old launch shape in it)
         elif plan["items"] is not None and not ctx.scatter_items_bound(plan["items"]):
@@ -1001,7 +1000,7 @@ class RayNetForwardPass(ForwardPass):
         # The same call as last time -- same scene object, range, model, options, sharding, the
         # cameras and feature maps the very objects (at the very addresses) the plan was built
         # from: the plan as it is.  ~10 identity checks instead of the bank, the neighbour lists,
-        # the pointer table and the plan key: 17 us of interpreter per pass (tools/pass_overhead.py:
+        # the pointer table and the plan key: 17 us of interpreter per pass (measured:
         # 198 -> 181 us for a pass whose kernels are a few us each), on the critical path of a
         # rank that waits for its map between two replays of its graph.
         gp_now = (gp.max_number_of_marched_voxels, gp.neighbors, gp.depth_planes, gp.gamma_mrf,

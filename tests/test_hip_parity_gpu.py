@@ -114,6 +114,35 @@ def test_similarities(torch, oracle_mod, case, generic):
     assert np.abs(S - c["S"]).max() <= tol        # (the stored host-side run: no pin, see the top)
 
 
+def test_similarities_beyond_64_kb_of_lds_in_two_contexts(torch, oracle_mod):
+    """A sweep whose workgroup needs more than 64 KB of dynamic LDS has to opt in per kernel
+    (hipFuncSetAttribute), and a context keeps for itself which kernels it has opted in: 32^3
+    voxels, M = 256, D = 3072 take 4 * (96 + 3076 + 4 * (3072 + 256)) = 65,936 bytes.  Two contexts
+    of that shape, created one after the other, both run K7, agree bit for bit and meet the oracle.
+    Both are on device 0: this holds the per-context path, it does not reproduce what a second
+    DEVICE did to the process-wide record this replaced."""
+    from raynet_amd.hip_implementations.context import HipContext
+    c = CU["wide"]
+    grid, M, D = (32, 32, 32), 256, 3072
+    assert 4 * (sum(grid) + (D + 4) // 4 * 4 + 4 * (D + M)) == 65936 > 64 * 1024
+    o = oracle_mod.Oracle(M=M, D=D, N=int(c["N"]), F=int(c["F"]), H=int(c["H"]), W=int(c["W"]),
+                          padding=int(c["padding"]), bbox=c["bbox"], grid_shape=grid)
+    assert o.F == 32                              # the cooperative sweep
+    rng = np.random.default_rng(int(c["seed"]))
+    feats = rng.standard_normal((o.N, o.H + o.padding + 1, o.W + o.padding + 1, o.F),
+                                dtype=np.float32) * np.float32(0.25)
+    So = o.similarities(feats, c["P"], c["starts"], c["ends"])
+    out = []
+    for k in range(2):
+        ctx = HipContext(M, D, o.N, o.F, o.H, o.W, o.padding, o.bbox, grid)
+        S = torch.zeros((len(c["starts"]), D), device="cuda")
+        ctx.compute_similarities(ctx.dev(feats), ctx.dev(c["P"]), ctx.dev(c["starts"]),
+                                 ctx.dev(c["ends"]), S)
+        out.append((ctx, S.cpu().numpy()))        # (the first context lives on while the second runs)
+    assert np.array_equal(out[0][1], out[1][1])
+    assert np.abs(out[0][1] - So).max() <= 1e-5   # test_similarities' bar for the cooperative sweep
+
+
 # ------------------------------------------------------------------ a3
 @pytest.mark.parametrize("case", sorted(TRAV))
 def test_traversal_bit_exact_vs_reference_cython(torch, oracle_mod, case):
