@@ -564,6 +564,29 @@ int rn_mesh_depthmap(rn_ctx *ctx, int32_t H, int32_t W, const float *P_pinv,
                      const float *camera_center, const float *nodes, const float *leaves,
                      float *depth_map, void *stream);
 
+/* The nearest point of the mesh for n query points (replaces the KD-tree query of
+ * raynet/pointcloud.py:63-72 behind metrics.py:155-236, which measures to the mesh's VERTICES):
+ * queries [n][3] f64.  The surface is the leaves' triangles p0, p0 + e1, p0 + e2 widened to
+ * float64; dist [n] f64 = the Euclidean distance to it, closest [n][3] f64 a point of the
+ * returned triangle that attains it, tri [n] that triangle's original index (closest and tri
+ * may be NULL).  A zero-area triangle is the segment or point it degenerates to. */
+int rn_mesh_closest(rn_ctx *ctx, int32_t n, const double *queries, const float *nodes,
+                    const float *leaves, double *dist, double *closest, int32_t *tri,
+                    void *stream);
+
+/* area [n] f64 = 0.5 |(p1 - p0) x (p2 - p0)| of triangles [n][9] f32, formed in float64. */
+int rn_mesh_areas(rn_ctx *ctx, int32_t n, const float *triangles, double *area, void *stream);
+
+/* n_samples stratified, area-weighted points of the surface (no counterpart in the
+ * reference): area_cdf [n_triangles] f64 is the inclusive running sum of rn_mesh_areas, its
+ * last entry > 0.  Sample k lies in the first triangle t with area_cdf[t] > (k + r0) /
+ * n_samples * area at p0 + r1 e1 + r2 e2 ((r1, r2) folded into the triangle), formed in
+ * float64 and rounded once: points [n_samples][3] f32, tri [n_samples].  r0, r1, r2 are a
+ * counter-based hash of (seed, k, j). */
+int rn_mesh_sample(rn_ctx *ctx, int32_t n_samples, int32_t n_triangles, const float *triangles,
+                   const double *area_cdf, int64_t seed, float *points, int32_t *tri,
+                   void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -171,6 +171,9 @@ SIGNATURES = {
     "rn_mesh_build": [_P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(_I), _P],
     "rn_mesh_raycast": [_P, _I, _P, _P, _P, _P, _P, _P, _P],
     "rn_mesh_depthmap": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_closest": [_P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_areas": [_P, _I, _P, _P, _P],
+    "rn_mesh_sample": [_P, _I, _I, _P, _P, _L, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

@@ -138,6 +138,11 @@ class Scene(object):
     def get_pointcloud(self):
         raise NotImplementedError()
 
+    def get_surface(self):
+        """The ground-truth SURFACE (a mesh.MeshRaycaster: closest_points, sample_surface) of a
+        scene that ships triangles; a scene that ships none has no such thing."""
+        raise NotImplementedError("%s has no ground-truth mesh" % type(self).__name__)
+
     @property
     def image_shape(self):
         im = self.get_image(0)
@@ -242,6 +247,11 @@ class RestrepoScene(Scene):
             points, _, faces = parse_gt_data(self._basepath)
             self._raycaster = MeshRaycaster(get_triangles(points, faces))
         return self._raycaster
+
+    def get_surface(self):
+        """The ground-truth mesh as a surface (mesh.MeshRaycaster), built once per scene;
+        NotImplementedError when the scene has no gt_mesh.obj / gt_mesh.ply."""
+        return self._get_raycaster()
 
     def get_depth_map(self, i):
         """gt/gt_depth_%d.npy if it exists, else the ground-truth mesh ray-cast on the GPU

@@ -13,6 +13,9 @@
 //   k_mesh_depth      the tree's depth (the traversal stack's guard)
 //   k_mesh_raycast    first intersection of explicit rays (one lane per ray)
 //   k_mesh_depthmap   first intersection of every pixel's ray -> distance map
+//   k_mesh_closest    the nearest point of the mesh for every query point (float64 leaf test)
+//   k_mesh_areas      triangle areas in float64
+//   k_mesh_sample     stratified, area-weighted points of the surface from a counter hash
 //
 // The intersection test restates fast_ray_triangles_intersection (fast_utils.pyx:47-117,
 // Moeller-Trumbore) operation for operation in fp32 with correctly rounded division and
@@ -368,6 +371,230 @@ __global__ __launch_bounds__(MESH_RAY_BLOCK) void k_mesh_depthmap(int H, int W, 
     depth[(size_t)v * W + u] = out;
 }
 
+// ---- nearest point on the mesh, areas, area-weighted surface samples -----------------------
+// The surface is the set of the leaves' triangles: a = p0, b = p0 + e1, c = p0 + e2, the fp32
+// leaf values widened to float64 (the triangles the ray cast intersects).
+
+struct MeshNear {
+    double d2;            // squared distance of the best triangle so far
+    double cx, cy, cz;    // the point of it that attains d2
+    int tri;              // its original index
+};
+
+// Closest point of one triangle to q in float64: the region classification of Ericson,
+// Real-Time Collision Detection 5.1.5.  An edge's region counts only where the edge has a length
+// (the quotient's denominator, its squared length, is > 0): with a == b every term of "edge ab"
+// is zero and the unguarded rule would claim every point; a collapsed edge is left to the vertex
+// regions and the other edges, so a triangle collapsed to a segment or a point is that segment
+// or point, and nothing here can form 0 / 0.
+__device__ __forceinline__ void mesh_closest_leaf(const MeshLeaf &L, double qx, double qy,
+                                                  double qz, MeshNear &best) {
+    const double ax = L.p0.x, ay = L.p0.y, az = L.p0.z;
+    const double abx = L.e1.x, aby = L.e1.y, abz = L.e1.z;
+    const double acx = L.e2.x, acy = L.e2.y, acz = L.e2.z;
+    const double apx = qx - ax, apy = qy - ay, apz = qz - az;
+    const double d1 = abx * apx + aby * apy + abz * apz;
+    const double d2 = acx * apx + acy * apy + acz * apz;
+    double v = 0., w = 0.;
+    if (!(d1 <= 0. && d2 <= 0.)) {                                        // else: vertex a
+        const double bpx = qx - (ax + abx), bpy = qy - (ay + aby), bpz = qz - (az + abz);
+        const double d3 = abx * bpx + aby * bpy + abz * bpz;
+        const double d4 = acx * bpx + acy * bpy + acz * bpz;
+        const double vc = d1 * d4 - d3 * d2;
+        if (d3 >= 0. && d4 <= d3) {                                       // vertex b
+            v = 1.;
+        } else if (vc <= 0. && d1 >= 0. && d3 <= 0. && d1 - d3 > 0.) {    // edge ab
+            v = d1 / (d1 - d3);
+        } else {
+            const double cpx = qx - (ax + acx), cpy = qy - (ay + acy), cpz = qz - (az + acz);
+            const double d5 = abx * cpx + aby * cpy + abz * cpz;
+            const double d6 = acx * cpx + acy * cpy + acz * cpz;
+            const double vb = d5 * d2 - d1 * d6;
+            const double va = d3 * d6 - d5 * d4;
+            if (d6 >= 0. && d5 <= d6) {                                   // vertex c
+                w = 1.;
+            } else if (vb <= 0. && d2 >= 0. && d6 <= 0. && d2 - d6 > 0.) {    // edge ac
+                w = d2 / (d2 - d6);
+            } else if (va <= 0. && d4 - d3 >= 0. && d5 - d6 >= 0. &&
+                       (d4 - d3) + (d5 - d6) > 0.) {                      // edge bc
+                w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+                v = 1. - w;
+            } else {                                                      // the face
+                const double den = va + vb + vc;
+                if (den > 0.) {
+                    v = fmin(fmax(vb / den, 0.), 1.);
+                    w = fmin(fmax(vc / den, 0.), 1. - v);
+                }
+            }
+        }
+    }
+    const double cx = (ax + v * abx) + w * acx, cy = (ay + v * aby) + w * acy,
+                 cz = (az + v * abz) + w * acz;
+    const double ex = qx - cx, ey = qy - cy, ez = qz - cz;
+    const double dd = ex * ex + ey * ey + ez * ez;
+    if (dd < best.d2) {
+        best.d2 = dd;
+        best.cx = cx;
+        best.cy = cy;
+        best.cz = cz;
+        best.tri = (int)__float_as_uint(L.p0.w);
+    }
+}
+
+// fp32 distance of (x, y, z) to a box, then made a lower bound of the float64 distance of the
+// query to anything in the box: shrunk by MESH_MARGIN of itself and by `m` (pruning only)
+__device__ __forceinline__ float mesh_box_lower(float4 lo, float4 hi, float x, float y, float z,
+                                                float m) {
+    const float dx = fmaxf(fmaxf(lo.x - x, x - hi.x), 0.f);
+    const float dy = fmaxf(fmaxf(lo.y - y, y - hi.y), 0.f);
+    const float dz = fmaxf(fmaxf(lo.z - z, z - hi.z), 0.f);
+    return sqrtf(dx * dx + dy * dy + dz * dz) * (1.f - MESH_MARGIN) - m;
+}
+
+// an fp32 upper bound of the best distance so far
+__device__ __forceinline__ float mesh_near_limit(const MeshNear &b) {
+    return sqrtf((float)b.d2) * (1.f + MESH_MARGIN);
+}
+
+// One lane per query.  The children of a node are tested when the node is taken up -- a popped
+// node is not tested again as a whole, its box is not stored in it: one fetch more for a
+// node the search has meanwhile overtaken, and the stack stays one 32-bit word per entry.
+__global__ __launch_bounds__(MESH_RAY_BLOCK) void k_mesh_closest(int n, const double *__restrict__ queries,
+                                                                 const MeshNode *__restrict__ nodes,
+                                                                 const MeshLeaf *__restrict__ leaves,
+                                                                 double *__restrict__ dist,
+                                                                 double *__restrict__ closest,
+                                                                 int32_t *__restrict__ tri) {
+    __shared__ uint32_t stack_all[MESH_STACK * MESH_RAY_BLOCK];
+    const int i = blockIdx.x * MESH_RAY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t *stack = stack_all + threadIdx.x;
+    const size_t o = 3 * (size_t)i;
+    const double qx = queries[o], qy = queries[o + 1], qz = queries[o + 2];
+    const float fx = (float)qx, fy = (float)qy, fz = (float)qz;
+    const MeshNode root = nodes[0];
+    const float scale = fmaxf(fmaxf(fmaxf(fabsf(root.a_lo.x), fabsf(root.a_lo.y)), fabsf(root.a_lo.z)),
+                              fmaxf(fmaxf(fabsf(root.a_hi.x), fabsf(root.a_hi.y)), fabsf(root.a_hi.z)));
+    const float scale_b = fmaxf(fmaxf(fmaxf(fabsf(root.b_lo.x), fabsf(root.b_lo.y)), fabsf(root.b_lo.z)),
+                                fmaxf(fmaxf(fabsf(root.b_hi.x), fabsf(root.b_hi.y)), fabsf(root.b_hi.z)));
+    // the absolute margin: rounding q to fp32 moves it by 2^-24 |q|, a leaf's b and c lie
+    // within 2^-23 of the scene's scale of the fp32 vertices the boxes hold
+    const float m = MESH_MARGIN * (fmaxf(scale, scale_b) +
+                                   fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)));
+    MeshNear b;
+    b.d2 = INFINITY;
+    b.cx = b.cy = b.cz = 0.;
+    b.tri = -1;
+    uint32_t node = 0;
+    int sp = 0;
+    while (true) {
+        const MeshNode nd = nodes[node];
+        const float da = mesh_box_lower(nd.a_lo, nd.a_hi, fx, fy, fz, m);
+        const float db = mesh_box_lower(nd.b_lo, nd.b_hi, fx, fy, fz, m);
+        const uint32_t ca = __float_as_uint(nd.a_lo.w), cb = __float_as_uint(nd.b_lo.w);
+        // (a child is skipped only where `lower > limit` holds: a NaN query skips nothing)
+        bool ha = true, hb = true;
+        if (ca & MESH_LEAF) {
+            if (!(da > mesh_near_limit(b))) mesh_closest_leaf(leaves[ca & ~MESH_LEAF], qx, qy, qz, b);
+            ha = false;
+        }
+        if (cb & MESH_LEAF) {
+            if (!(db > mesh_near_limit(b))) mesh_closest_leaf(leaves[cb & ~MESH_LEAF], qx, qy, qz, b);
+            hb = false;
+        }
+        const float lim = mesh_near_limit(b);
+        ha = ha && !(da > lim);
+        hb = hb && !(db > lim);
+        if (ha && hb) {
+            const bool a_first = da <= db;
+            stack[sp * MESH_RAY_BLOCK] = a_first ? cb : ca;
+            sp++;
+            node = a_first ? ca : cb;
+        } else if (ha) {
+            node = ca;
+        } else if (hb) {
+            node = cb;
+        } else {
+            if (sp == 0) break;
+            sp--;
+            node = stack[sp * MESH_RAY_BLOCK];
+        }
+    }
+    dist[i] = sqrt(b.d2);
+    if (closest) {
+        closest[o] = b.cx;
+        closest[o + 1] = b.cy;
+        closest[o + 2] = b.cz;
+    }
+    if (tri) tri[i] = b.tri;
+}
+
+// area[t] = 0.5 |e1 x e2| in float64, e1 = p1 - p0 and e2 = p2 - p0 formed in float64 from the
+// fp32 vertices of triangle t ([n][9], the caller's order)
+__global__ __launch_bounds__(BLOCK) void k_mesh_areas(int n, const float *__restrict__ tris,
+                                                      double *__restrict__ area) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *t = tris + (size_t)9 * i;
+    const double e1x = (double)t[3] - (double)t[0], e1y = (double)t[4] - (double)t[1],
+                 e1z = (double)t[5] - (double)t[2];
+    const double e2x = (double)t[6] - (double)t[0], e2y = (double)t[7] - (double)t[1],
+                 e2z = (double)t[8] - (double)t[2];
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    area[i] = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
+}
+
+// splitmix64's output function (Steele, Lea, Flood 2014)
+__host__ __device__ __forceinline__ unsigned long long mesh_mix64(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// r_j of sample k in [0, 1): the top 53 bits of
+// mix64(mix64(seed + G) + G * (3 k + j + 1)), G = 0x9E3779B97F4A7C15, all modulo 2^64
+__device__ __forceinline__ double mesh_uniform(unsigned long long seed_key, int k, int j) {
+    const unsigned long long h =
+        mesh_mix64(seed_key + 0x9E3779B97F4A7C15ull * (3ull * (unsigned long long)k + (unsigned long long)j + 1ull));
+    return (double)(h >> 11) * 0x1.0p-53;
+}
+
+// stratified, area-weighted surface samples: sample k sits at x = (k + r0) / n * area of the
+// running area and falls into the first triangle t with area_cdf[t] > x
+__global__ __launch_bounds__(BLOCK) void k_mesh_sample(int n, int n_tri, const float *__restrict__ tris,
+                                                       const double *__restrict__ area_cdf,
+                                                       unsigned long long seed_key,
+                                                       float *__restrict__ points,
+                                                       int32_t *__restrict__ tri) {
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const double total = area_cdf[n_tri - 1];
+    const double r0 = mesh_uniform(seed_key, k, 0), r1 = mesh_uniform(seed_key, k, 1),
+                 r2 = mesh_uniform(seed_key, k, 2);
+    double x = ((double)k + r0) / (double)n * total;
+    // (k + r0) / n may round up to 1: keep x below the total, so that a triangle with
+    // area_cdf[t] > x exists (total > 0, the caller's check)
+    if (!(x < total)) x = __longlong_as_double(__double_as_longlong(total) - 1);
+    int lo = 0, hi = n_tri - 1;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (area_cdf[mid] > x)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    const float *t = tris + (size_t)9 * lo;
+    const bool fold = r1 + r2 > 1.;
+    const double u = fold ? 1. - r1 : r1, v = fold ? 1. - r2 : r2;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double p0 = (double)t[c];
+        const double e1 = (double)t[3 + c] - p0, e2 = (double)t[6 + c] - p0;
+        points[3 * (size_t)k + c] = (float)((p0 + u * e1) + v * e2);
+    }
+    tri[k] = lo;
+}
+
 constexpr int MESH_MAX_TRIANGLES = 1 << 30;
 
 }  // namespace
@@ -444,6 +671,40 @@ int rn_mesh_depthmap(rn_ctx *ctx, int32_t H, int32_t W, const float *P_pinv,
                        dim3(MESH_RAY_BLOCK), 0, S(stream), H, W, P_pinv, camera_center,
                        reinterpret_cast<const MeshNode *>(nodes),
                        reinterpret_cast<const MeshLeaf *>(leaves), depth_map);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mesh_closest(rn_ctx *ctx, int32_t n, const double *queries, const float *nodes,
+                    const float *leaves, double *dist, double *closest, int32_t *tri,
+                    void *stream) {
+    RN_OPEN(ctx, n, all_set(queries, nodes, leaves, dist));
+    hipLaunchKernelGGL(k_mesh_closest, dim3((n + MESH_RAY_BLOCK - 1) / MESH_RAY_BLOCK),
+                       dim3(MESH_RAY_BLOCK), 0, S(stream), n, queries,
+                       reinterpret_cast<const MeshNode *>(nodes),
+                       reinterpret_cast<const MeshLeaf *>(leaves), dist, closest, tri);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mesh_areas(rn_ctx *ctx, int32_t n, const float *triangles, double *area, void *stream) {
+    if (!ctx || n < 1 || n > MESH_MAX_TRIANGLES || !triangles || !area)
+        return fail(ctx, RN_ERR_INVALID, "bad argument");
+    hipLaunchKernelGGL(k_mesh_areas, dim3(thread_blocks(n)), dim3(BLOCK), 0, S(stream), n, triangles,
+                       area);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mesh_sample(rn_ctx *ctx, int32_t n_samples, int32_t n_triangles, const float *triangles,
+                   const double *area_cdf, int64_t seed, float *points, int32_t *tri,
+                   void *stream) {
+    RN_OPEN(ctx, n_samples, n_triangles >= 1 && n_triangles <= MESH_MAX_TRIANGLES &&
+                                all_set(triangles, area_cdf, points, tri));
+    const unsigned long long seed_key =
+        mesh_mix64((unsigned long long)seed + 0x9E3779B97F4A7C15ull);
+    hipLaunchKernelGGL(k_mesh_sample, dim3(thread_blocks(n_samples)), dim3(BLOCK), 0, S(stream),
+                       n_samples, n_triangles, triangles, area_cdf, seed_key, points, tri);
     RN_LAUNCH_CHECK(ctx);
     return RN_OK;
 }

@@ -394,6 +394,32 @@ class HipContext(object):
                                              _ptr(nodes), _ptr(leaves), _ptr(points), _ptr(tri),
                                              _stream()))
 
+    def mesh_closest(self, queries, nodes, leaves, dist, closest=None, tri=None):
+        n = queries.shape[0]
+        _chk(queries, torch.float64, 3 * n, "queries", align=8)
+        _chk(dist, torch.float64, n, "dist", align=8)
+        _chk(closest, torch.float64, 3 * n, "closest", optional=True, align=8)
+        _chk(tri, torch.int32, n, "tri", optional=True)
+        _chk(nodes, torch.float32, 16, "nodes", align=16)
+        _chk(leaves, torch.float32, 12, "leaves", align=16)
+        self._check(self.lib.rn_mesh_closest(self._h, n, _ptr(queries), _ptr(nodes), _ptr(leaves),
+                                             _ptr(dist), _ptr(closest), _ptr(tri), _stream()))
+
+    def mesh_areas(self, triangles, area):
+        n = triangles.shape[0]
+        _chk(triangles, torch.float32, 9 * n, "triangles")
+        _chk(area, torch.float64, n, "area", align=8)
+        self._check(self.lib.rn_mesh_areas(self._h, n, _ptr(triangles), _ptr(area), _stream()))
+
+    def mesh_sample(self, triangles, area_cdf, seed, points, tri):
+        n, T = tri.shape[0], triangles.shape[0]
+        _chk(triangles, torch.float32, 9 * T, "triangles")
+        _chk(area_cdf, torch.float64, T, "area_cdf", align=8)
+        _chk(points, torch.float32, 3 * n, "points")
+        _chk(tri, torch.int32, n, "tri")
+        self._check(self.lib.rn_mesh_sample(self._h, n, T, _ptr(triangles), _ptr(area_cdf),
+                                            int(seed), _ptr(points), _ptr(tri), _stream()))
+
     def mesh_depthmap(self, H, W, P_pinv, center, nodes, leaves, depth_map):
         _chk(P_pinv, torch.float32, 12, "P_pinv")
         _chk(center, torch.float32, 3, "center")

@@ -13,6 +13,10 @@ whole batches of rays through it (include/raynet_hip.h, rn_mesh_*; DESIGN.md sec
     float64 from the fp32 P_pinv and rounded once to fp32 (`pixel_destinations`);
   * a depth is the float64 distance of the hit to the camera centre (geometry.distance).
 
+`closest_points` measures to the SURFACE (the reference's metrics measure to the mesh's vertices,
+metrics.py:155-236) and `sample_surface` draws area-weighted points of it, for
+metrics.SurfaceAccuracy / SurfaceCompleteness.
+
 There is no CPU route: without a GPU the constructor raises RaynetHipError.
 """
 import time
@@ -87,6 +91,7 @@ class MeshRaycaster(object):
             work = torch.empty((56 * n + 64,), dtype=torch.uint8, device=self.device)
             self.depth = self._ctx.mesh_build(self.triangles, keys, self.nodes, self.leaves, work)
             self.build_ms = (time.perf_counter() - t0) * 1e3
+        self._area_cdf = None
 
     def first_intersections(self, origins, destinations):
         """First hits of the rays origins[i] -> destinations[i] ([n, 3] f32, host or device):
@@ -122,6 +127,61 @@ class MeshRaycaster(object):
         points, tri = self.first_intersections(o, dst)
         tri = tri.cpu().numpy()
         return hit_depths(points.cpu().numpy(), tri >= 0, camera.center)
+
+    def closest_points(self, points):
+        """The nearest point of the surface for every row of `points` ([n, 3], host or device,
+        any float dtype; taken as float64): device tensors (dist f64 [n], closest f64 [n, 3],
+        tri int32 [n]).  The surface is the leaves' triangles p0, p0 + e1, p0 + e2 in float64
+        -- the triangles the rays hit; a zero-area triangle is the segment or point it is."""
+        if isinstance(points, torch.Tensor):
+            q = points.detach().to(device=self.device, dtype=torch.float64)
+        else:
+            q = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).to(self.device)
+        if q.dim() != 2 or q.shape[1] != 3:
+            raise ValueError("points: expected [n, 3], got %s" % (tuple(q.shape),))
+        q = q.contiguous()
+        n = q.shape[0]
+        dist = torch.empty((n,), dtype=torch.float64, device=self.device)
+        closest = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+        tri = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ctx.mesh_closest(q, self.nodes, self.leaves, dist, closest, tri)
+        return dist, closest, tri
+
+    @property
+    def area_cdf(self):
+        """Inclusive running sum [T] f64 (device) of the triangles' areas 0.5 |e1 x e2| in the
+        caller's triangle order, taken once."""
+        if self._area_cdf is None:
+            with torch.cuda.device(self.device):
+                areas = torch.empty((self.n_triangles,), dtype=torch.float64, device=self.device)
+                self._ctx.mesh_areas(self.triangles, areas)
+                self._area_cdf = torch.cumsum(areas, 0).contiguous()
+        return self._area_cdf
+
+    @property
+    def area(self):
+        """The surface's area (a Python float): the last entry of `area_cdf`."""
+        return float(self.area_cdf[-1].item())
+
+    def sample_surface(self, n_samples, seed=0):
+        """`n_samples` stratified, area-weighted points of the surface: (points f32 [n, 3],
+        tri int32 [n]) as device tensors, the same for the same mesh, n_samples and seed.
+        Sample k lies in the first triangle t with area_cdf[t] > (k + r0) / n * area (so never in
+        a zero-area one) at p0 + r1 e1 + r2 e2; the hash behind r0, r1, r2: DESIGN.md section 14."""
+        n = int(n_samples)
+        if n < 0 or n > (1 << 30):
+            raise ValueError("n_samples: 0 .. 2^30, got %d" % n)
+        seed = int(seed)
+        if not -(1 << 63) <= seed < (1 << 63):
+            raise ValueError("seed: a signed 64-bit integer")
+        if n and not self.area > 0.0:
+            raise ValueError("the mesh has no area to sample (%r)" % self.area)
+        points = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        tri = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ctx.mesh_sample(self.triangles, self.area_cdf, seed, points, tri)
+        return points, tri
 
     def _dev3(self, x, name):
         if isinstance(x, torch.Tensor):

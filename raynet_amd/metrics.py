@@ -1,6 +1,11 @@
 """Evaluation metrics of the reference (raynet/metrics.py:130-236) on MI355X: the same
 classes and `compute(scene, frame_idxs, depthmaps, predicted_pointcloud)` signature; the
-nearest-neighbour distances come from the HIP scan behind `Pointcloud.nearest_neighbors`."""
+nearest-neighbour distances come from the HIP scan behind `Pointcloud.nearest_neighbors`.
+
+`Accuracy` / `Completeness` measure to and from the ground-truth mesh's VERTICES, as the
+reference does; on meshes of large flat triangles a point that lies exactly on a wall is then
+far from the ground truth.  `SurfaceAccuracy` / `SurfaceCompleteness` measure to the mesh's
+surface and from area-weighted samples of it (scene.get_surface(), raynet_amd/mesh.py)."""
 import numpy as np
 
 from .pointcloud import Pointcloud, PointcloudFromDepthMaps  # noqa: F401
@@ -87,6 +92,47 @@ class Completeness(_CloudMetric):
 
     def compute(self, scene, frame_idxs, depthmaps, predicted_pointcloud):
         ground_truth_pc = self._clouds(scene, frame_idxs, predicted_pointcloud)
+        predicted_pointcloud.index()
+        distances, indexes = predicted_pointcloud.nearest_neighbors(ground_truth_pc.points)
+        return np.minimum(distances, self.truncate), ground_truth_pc.points
+
+
+class SurfaceAccuracy(Metric):
+    """Distance of every predicted point to the ground-truth SURFACE
+    (scene.get_surface().closest_points, float64): -> ((N, 1) distances, predicted points)
+    like Accuracy.  A scene without a mesh raises NotImplementedError."""
+
+    def __init__(self, filter_factory=None, truncate=float("inf")):
+        self.filter_factory = filter_factory if filter_factory is not None else FiltersFactory([])
+        self.truncate = truncate
+
+    def compute(self, scene, frame_idxs, depthmaps, predicted_pointcloud):
+        surface = scene.get_surface()
+        if self.filter_factory.has_filters:
+            predicted_pointcloud.filter(self.filter_factory)
+        points = predicted_pointcloud.points
+        dist, _, _ = surface.closest_points(np.asarray(points).T)
+        distances = dist.cpu().numpy().reshape(-1, 1)
+        return np.minimum(distances, self.truncate), points
+
+
+class SurfaceCompleteness(Metric):
+    """Distance of `n_samples` area-weighted samples of the ground-truth surface
+    (scene.get_surface().sample_surface(n_samples, seed)) to the prediction: from the samples
+    on, Completeness."""
+
+    def __init__(self, n_samples, seed=0, filter_factory=None, truncate=float("inf")):
+        self.n_samples = n_samples
+        self.seed = seed
+        self.filter_factory = filter_factory if filter_factory is not None else FiltersFactory([])
+        self.truncate = truncate
+
+    def compute(self, scene, frame_idxs, depthmaps, predicted_pointcloud):
+        samples, _ = scene.get_surface().sample_surface(self.n_samples, self.seed)
+        ground_truth_pc = Pointcloud(np.ascontiguousarray(samples.cpu().numpy().T))
+        if self.filter_factory.has_filters:
+            ground_truth_pc.filter(self.filter_factory)
+            predicted_pointcloud.filter(self.filter_factory)
         predicted_pointcloud.index()
         distances, indexes = predicted_pointcloud.nearest_neighbors(ground_truth_pc.points)
         return np.minimum(distances, self.truncate), ground_truth_pc.points
