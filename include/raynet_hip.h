@@ -587,6 +587,47 @@ int rn_mesh_sample(rn_ctx *ctx, int32_t n_samples, int32_t n_triangles, const fl
                    const double *area_cdf, int64_t seed, float *points, int32_t *tri,
                    void *stream);
 
+/* ---- point-cloud filters ------------------------------
+ * The two filters the reference's evaluation puts between a cloud and its score.  Points are
+ * [3][n] f64, planar, as rn_depthmap_points writes them; n == 0 is an empty launch. */
+
+/* VoxelMask.filter (raynet/metrics.py:55-75 with keep_points_in_aabbox / point_in_aabbox,
+ * utils/geometry.py:238-240, 315-348): keep [n] u8 = 1 where min <= p <= max on every axis
+ * and mask[ix][iy][iz] == 1, i = rint((p - min - step / 2) / step) (half to even, like
+ * np.round).  box [12] f64 (device): min xyz | max xyz | step xyz | step / 2 xyz, as NumPy
+ * forms them from the float32 bounding box; mask [A][B][C] u8, C-ordered.  One deviation: on
+ * the max face of an axis with an even voxel count the reference's index equals the count and
+ * it raises IndexError; here the index is clamped to count - 1. */
+int rn_voxel_mask(rn_ctx *ctx, int32_t n, const double *points, const double *box, int32_t A,
+                  int32_t B, int32_t C, const uint8_t *mask, uint8_t *keep, void *stream);
+
+/* ReduceDensity.filter (raynet/metrics.py:94-127), step 1 (replaces KDTree(X.T), :106, and the
+ * shuffle, :102-103): keys [n] = (cx + 1) << 42 | (cy + 1) << 21 | (cz + 1) with
+ * c = floor((p - lo) / h) per axis in float64 -- the caller guarantees 0 <= c <= 2^21 - 3 --
+ * and the visiting priority [n], smaller = visited earlier, compared as unsigned 64-bit and
+ * then by the point's index: position[i] where position (device, [n] i64: the place of point
+ * i in an explicit visiting order) is given, else the counter hash
+ *     mix64(mix64(seed + G) + G * (i + 1)),   G = 0x9E3779B97F4A7C15,   all modulo 2^64,
+ *     mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *               z ^ z >> 31   (splitmix64's output function, as rn_mesh_sample uses it). */
+int rn_thin_keys(rn_ctx *ctx, int32_t n, const double *points, double lo_x, double lo_y,
+                 double lo_z, double h, int64_t seed, const int64_t *position, int64_t *keys,
+                 int64_t *priority, void *stream);
+
+/* Step 2 (replaces query_radius and the loop, metrics.py:109-119): one round over the n_work
+ * points work [n_work] i32 names (NULL: all n) of arrays in ascending key order -- sorted_keys
+ * [n], points [3][n], priority [n], index [n] i32 (the points' original indices).  An
+ * undecided point (state 0) becomes removed (2) if an earlier neighbour -- dx*dx + dy*dy +
+ * dz*dz <= r2, uncontracted -- is kept (1), kept if every earlier neighbour is removed;
+ * neighbours are searched in the 27 cells around it, so h > sqrt(r2).  state [n] i32 is
+ * updated in place (zero it before the first round); *undecided (device i32, zeroed by the
+ * caller) += the points of the work list still undecided.  Rounds repeated until that is 0
+ * leave exactly the reference's kept set for the same visiting order. */
+int rn_thin_round(rn_ctx *ctx, int32_t n_work, const int32_t *work, int32_t n,
+                  const int64_t *sorted_keys, const double *points, const int64_t *priority,
+                  const int32_t *index, double r2, int32_t *state, int32_t *undecided,
+                  void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -1126,3 +1126,6 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 
 // ground-truth depth from scene meshes (BVH ray casting)
 #include "raynet_mesh.inl"
+
+// point-cloud filters: VoxelMask and the exact parallel ReduceDensity
+#include "raynet_filters.inl"

@@ -358,6 +358,44 @@ class HipContext(object):
                                                   query_xyzw.shape[0], _ptr(query_xyzw),
                                                   _ptr(dist), _ptr(idx), _stream()))
 
+    # ---- point-cloud filters (raynet_amd/metrics.py: VoxelMask, ReduceDensity) ------------
+    def voxel_mask(self, points, box, mask, keep):
+        """points (3, n) f64, box [12] f64 (min | max | step | step / 2), mask (A, B, C) u8."""
+        n = points.shape[1]
+        A, B, C = (int(s) for s in mask.shape)
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        _chk(box, torch.float64, 12, "box", align=8)
+        _chk(mask, torch.uint8, A * B * C, "mask", align=1)
+        _chk(keep, torch.uint8, n, "keep", align=1)
+        self._check(self.lib.rn_voxel_mask(self._h, n, _ptr(points), _ptr(box), A, B, C,
+                                           _ptr(mask), _ptr(keep), _stream()))
+
+    def thin_keys(self, points, lo, h, seed, position, keys, priority):
+        """Cell keys and visiting priorities of points (3, n) f64; position: None or [n] i64."""
+        n = points.shape[1]
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        _chk(position, torch.int64, n, "position", optional=True, align=8)
+        _chk(keys, torch.int64, n, "keys", align=8)
+        _chk(priority, torch.int64, n, "priority", align=8)
+        self._check(self.lib.rn_thin_keys(self._h, n, _ptr(points), float(lo[0]), float(lo[1]),
+                                          float(lo[2]), float(h), int(seed), _ptr(position),
+                                          _ptr(keys), _ptr(priority), _stream()))
+
+    def thin_round(self, work, sorted_keys, points, priority, index, r2, state, undecided):
+        """One round over `work` (None: all points) of the arrays in key order."""
+        n = points.shape[1]
+        n_work = n if work is None else work.shape[0]
+        _chk(work, torch.int32, n_work, "work", optional=True)
+        _chk(sorted_keys, torch.int64, n, "sorted_keys", align=8)
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        _chk(priority, torch.int64, n, "priority", align=8)
+        _chk(index, torch.int32, n, "index")
+        _chk(state, torch.int32, n, "state")
+        _chk(undecided, torch.int32, 1, "undecided")
+        self._check(self.lib.rn_thin_round(self._h, n_work, _ptr(work), n, _ptr(sorted_keys),
+                                           _ptr(points), _ptr(priority), _ptr(index), float(r2),
+                                           _ptr(state), _ptr(undecided), _stream()))
+
     KERNEL_NAMES = {1: "traverse", 2: "sweep_map", 3: "bp", 4: "depth", 5: "acc", 6: "other", 7: "scatter"}
 
     # ---- ground truth from scene meshes (raynet_amd/mesh.py) ----------------------------

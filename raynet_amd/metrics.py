@@ -5,7 +5,14 @@ nearest-neighbour distances come from the HIP scan behind `Pointcloud.nearest_ne
 `Accuracy` / `Completeness` measure to and from the ground-truth mesh's VERTICES, as the
 reference does; on meshes of large flat triangles a point that lies exactly on a wall is then
 far from the ground truth.  `SurfaceAccuracy` / `SurfaceCompleteness` measure to the mesh's
-surface and from area-weighted samples of it (scene.get_surface(), raynet_amd/mesh.py)."""
+surface and from area-weighted samples of it (scene.get_surface(), raynet_amd/mesh.py).
+
+`VoxelMask` / `ReduceDensity` are the reference's two filters (raynet/metrics.py:27-127) for a
+`FiltersFactory`; the thinning runs as exact parallel rounds on the GPU (DESIGN.md section
+12a) and, unlike the reference's unseeded shuffle, in a reproducible visiting order."""
+import os
+import time
+
 import numpy as np
 
 from .pointcloud import Pointcloud, PointcloudFromDepthMaps  # noqa: F401
@@ -25,6 +32,200 @@ class FiltersFactory(object):
         for f in self.filters:
             X = f.filter(X)
         return X
+
+
+def _as_points(X):
+    """(3, N) NumPy array or tensor -> (3, N) float64 NumPy array (float32 is widened)."""
+    if hasattr(X, "detach"):
+        X = X.detach().cpu().numpy()
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[0] != 3:
+        raise ValueError("points must be (3, N), got %s" % (X.shape,))
+    return np.ascontiguousarray(X, dtype=np.float64)
+
+
+def _filtered(X, keep, output_directory, file_name):
+    """The reference's tail of a filter: the kept columns in their original order, its
+    message, and the PLY when an output directory is set."""
+    points = np.ascontiguousarray(X[:, keep])
+    print("Filter out %d out of %d points" % (X.shape[1] - points.shape[1], X.shape[1]))
+    if output_directory is not None:
+        Pointcloud(points).save_ply(os.path.join(output_directory, file_name))
+    return points
+
+
+class VoxelMask(object):
+    """raynet/metrics.py:27-75: keep the points inside the closed bounding box whose voxel of
+    `mask` is 1.  bbox: (1, 6); mask: (A, B, C).  One deviation: a point on the max face of an
+    axis with an even voxel count indexes one past the mask in the reference (IndexError);
+    here that index is clamped to the last voxel."""
+
+    def __init__(self, bbox, mask, output_directory=None):
+        bbox = np.asarray(bbox)
+        mask = np.asarray(mask)
+        if bbox.shape != (1, 6) or mask.ndim != 3:
+            raise ValueError("bbox must be (1, 6) and mask (A, B, C)")
+        if not np.all(bbox[0, :3] < bbox[0, 3:]):
+            raise ValueError("bbox: min must be below max on every axis")
+        self._bbox_min = bbox[0, :3, np.newaxis]
+        self._bbox_max = bbox[0, 3:, np.newaxis]
+        self._grid_shape = np.array(mask.shape).reshape(3, 1)
+        self._mask = mask
+        # NumPy's own promotion: the float32 difference over the int64 shape is float64
+        self._steps = (self._bbox_max - self._bbox_min) / self._grid_shape
+        self.output_directory = output_directory
+
+    def _box(self):
+        """min | max | step | step / 2 as the float64 values NumPy uses next to float64 points."""
+        return np.concatenate([a.astype(np.float64).ravel() for a in (
+            self._bbox_min, self._bbox_max, self._steps, self._steps / 2)])
+
+    def filter(self, X):
+        import torch
+        from .hip_implementations import get_context
+        X = _as_points(X)
+        N = X.shape[1]
+        if N == 0:
+            return _filtered(X, np.zeros((0,), bool), self.output_directory,
+                             "pc_inside_voxel_mask.ply")
+        keep = torch.empty((N,), dtype=torch.uint8, device="cuda")
+        get_context().voxel_mask(
+            torch.from_numpy(X).cuda(), torch.from_numpy(self._box()).cuda(),
+            torch.from_numpy(np.ascontiguousarray(self._mask == 1).view(np.uint8)).cuda(), keep)
+        return _filtered(X, keep.cpu().numpy().astype(bool), self.output_directory,
+                         "pc_inside_voxel_mask.ply")
+
+
+_MASK64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    """splitmix64's output function on a uint64 array (modulo 2^64)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def priority_hash(seed, n):
+    """The visiting priorities k_thin_keys gives n points without an explicit order:
+    mix64(mix64(seed + G) + G * (i + 1)), uint64 (include/raynet_hip.h: rn_thin_keys)."""
+    key = _mix64(np.array([(int(seed) + _GOLDEN) & _MASK64], np.uint64))
+    return _mix64(key + np.uint64(_GOLDEN) * np.arange(1, n + 1, dtype=np.uint64))
+
+
+class ReduceDensity(object):
+    """raynet/metrics.py:78-127: thin a cloud so that no two kept points are within `min_dist`
+    (dx*dx + dy*dy + dz*dz <= min_dist*min_dist in float64): visiting the points in an order,
+    a point is kept iff no earlier-visited kept point is that close.  The reference shuffles
+    with NumPy's unseeded global generator; here the order is the hash of (seed, index) --
+    ascending `priority_hash(seed, N)`, ties by index -- or `order`, a permutation of range(N)
+    visited first to last, which reproduces any given order (the reference's included)."""
+
+    CELL_BITS = 21
+    MAX_CELL = (1 << 21) - 3          # largest cell index per axis: its +1 neighbour, +1, fits
+
+    def __init__(self, min_dist, output_directory=None, seed=0, order=None):
+        if not min_dist > 0:
+            raise ValueError("min_dist must be positive, got %r" % (min_dist,))
+        self._min_dist = float(min_dist)
+        self.output_directory = output_directory
+        self.seed = int(seed)
+        self.order = None if order is None else np.asarray(order)
+        self.rounds = None            # rounds the last filter() took ...
+        self.round_seconds = None     # ... and each one's wall time, its count's read included
+
+    def visiting_order(self, n):
+        """The order in use for n points: indices, first visited first."""
+        if self.order is not None:
+            return self._checked_order(n)
+        return np.argsort(priority_hash(self.seed, n), kind="stable")
+
+    def _checked_order(self, n):
+        order = self.order
+        ok = order.ndim == 1 and order.shape[0] == n and order.dtype.kind in "iu"
+        if ok and n:
+            order = order.astype(np.int64)
+            ok = order.min() >= 0 and order.max() < n and \
+                bool(np.all(np.bincount(order, minlength=n) == 1))
+        if not ok:
+            raise ValueError("order must be a permutation of range(%d)" % n)
+        return order.astype(np.int64)
+
+    def _grid(self, X):
+        """(lo, h) of the search grid; ValueError for what the keys cannot hold."""
+        if not np.isfinite(X).all():
+            raise ValueError("points have non-finite coordinates")
+        h = self._min_dist * (1.0 + 2.0 ** -20)
+        lo = X.min(axis=1)
+        ratio = (X.max(axis=1) - lo) / h
+        for axis in range(3):
+            if not np.floor(ratio[axis]) <= self.MAX_CELL:
+                raise ValueError(
+                    "the cloud's extent over the cell size is %.6g on axis %d; the cell keys "
+                    "hold %d bits per axis, so it must stay below %d: choose a larger min_dist "
+                    "or cut the cloud first (VoxelMask)"
+                    % (ratio[axis], axis, self.CELL_BITS, self.MAX_CELL + 1))
+        return lo, h
+
+    def keep_mask(self, points, lo, h, position=None):
+        """The device part: points (3, N) float64 CUDA tensor, position None or the (N,) int64
+        CUDA tensor of every point's place in the order -> (N,) bool CUDA tensor of the kept
+        points.  Synchronises once per round (the count of undecided points)."""
+        import torch
+        from .hip_implementations import get_context
+        ctx = get_context()
+        N = points.shape[1]
+        keys = torch.empty((N,), dtype=torch.int64, device="cuda")
+        priority = torch.empty((N,), dtype=torch.int64, device="cuda")
+        ctx.thin_keys(points, lo, h, self.seed, position, keys, priority)
+        # cell order: neighbouring lanes hold neighbouring points
+        keys, perm = torch.sort(keys)
+        points = points[:, perm].contiguous()
+        priority = priority[perm].contiguous()
+        index = perm.to(torch.int32)
+        state = torch.zeros((N,), dtype=torch.int32, device="cuda")
+        undecided = torch.zeros((1,), dtype=torch.int32, device="cuda")
+        r2 = self._min_dist * self._min_dist
+        torch.cuda.current_stream().synchronize()     # round_seconds[0] is the round's alone
+        work, rounds, seconds = None, 0, []
+        while True:
+            t0 = time.perf_counter()
+            undecided.zero_()
+            ctx.thin_round(work, keys, points, priority, index, r2, state, undecided)
+            rounds += 1
+            left = int(undecided.item())
+            seconds.append(time.perf_counter() - t0)
+            if left == 0:
+                break
+            if rounds > N:
+                raise RuntimeError("the thinning did not settle in N rounds")
+            if work is None:
+                work = torch.nonzero(state == 0).view(-1).to(torch.int32)
+            else:
+                work = work[state[work.long()] == 0].contiguous()
+        self.rounds, self.round_seconds = rounds, seconds
+        keep = torch.empty((N,), dtype=torch.bool, device="cuda")
+        keep[perm] = state == 1
+        return keep
+
+    def filter(self, X):
+        import torch
+        X = _as_points(X)
+        N = X.shape[1]
+        position = None
+        if self.order is not None:
+            order = self._checked_order(N)
+            position = np.empty((N,), np.int64)
+            position[order] = np.arange(N, dtype=np.int64)
+        if N == 0:
+            keep = np.zeros((0,), bool)
+        else:
+            lo, h = self._grid(X)
+            keep = self.keep_mask(torch.from_numpy(X).cuda(), lo, h,
+                                  None if position is None else torch.from_numpy(position).cuda())
+            keep = keep.cpu().numpy()
+        return _filtered(X, keep, self.output_directory, "pc_after_density_reduction.ply")
 
 
 class Metric(object):

@@ -45,6 +45,25 @@ class Pointcloud(object):
                      "end_header\n" % (sys.byteorder, N)).encode())
             np.asarray(self.points).T.astype(np.float32).tofile(f)
 
+    def save_colored_ply(self, file, intensities, colormap="jet"):
+        """raynet/pointcloud.py:32-57: xyz float32 then uchar RGB per vertex, the colour of
+        matplotlib's `colormap` at intensity / 2 (one value per point)."""
+        from matplotlib import colormaps
+        N = self.points.shape[1]
+        values = np.asarray(intensities, np.float64).ravel() / 2
+        if values.shape[0] != N:
+            raise ValueError("%d intensities for %d points" % (values.shape[0], N))
+        colors = (colormaps[colormap](values)[:, :-1] * 255).astype(np.uint8)
+        vertices = np.empty((N,), dtype=[("xyz", np.float32, 3), ("rgb", np.uint8, 3)])
+        vertices["xyz"] = np.asarray(self.points).T
+        vertices["rgb"] = colors
+        with open(file, "wb") as f:
+            f.write(("ply\nformat binary_%s_endian 1.0\ncomment Raynet pointcloud!\n"
+                     "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                     "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                     "end_header\n" % (sys.byteorder, N)).encode())
+            vertices.tofile(f)
+
     def save(self, file):
         np.save(file, self.points)
 

@@ -15,10 +15,12 @@ as OUTPUT_DIR/predicted_pc_s_%d.ply and prints `name mean: ... median: ...` per 
                           -> nearest predicted point
 
 DATASET_DIR is the scene's directory (Restrepo) or the DTU root with --scene_idx, as for
-raynet_amd.scripts.forward_pass.  The flags are the reference's, with its defaults.  Not here,
-because this package has no such thing: the VoxelMask / ReduceDensity filters (--min_distance;
-the metrics run with an empty FiltersFactory) and the PLY coloured by the metric's value
-(Pointcloud.save_colored_ply).
+raynet_amd.scripts.forward_pass.  The flags are the reference's, with its defaults, but for
+--min_distance: the VoxelMask / ReduceDensity filters live in raynet_amd.metrics, their factory
+(`build_filter_factory`) and the --min_distance flag in raynet_amd.scripts.convert_to_pointcloud,
+and `run(scene, args, filter_factory=...)` here hands a factory to every cloud metric; from
+the command line the metrics run with an empty FiltersFactory.  The PLY coloured by a metric's
+value is Pointcloud.save_colored_ply.
 """
 import argparse
 import os
@@ -73,11 +75,11 @@ def build_parser():
     return p
 
 
-def build_metric(name, args):
+def build_metric(name, args, filter_factory=None):
     from raynet_amd.metrics import (Accuracy, Completeness, FiltersFactory,
                                     PerPixelMeanDepthError, SurfaceAccuracy,
                                     SurfaceCompleteness)
-    filters = FiltersFactory([])
+    filters = filter_factory if filter_factory is not None else FiltersFactory([])
     if name == "ppmde":
         return PerPixelMeanDepthError(args.borders)
     if name == "accuracy":
@@ -107,8 +109,9 @@ def main(argv=None):
     return run(scene, args)
 
 
-def run(scene, args):
-    """The script's body on a scene object (`args`: the parser's namespace)."""
+def run(scene, args, filter_factory=None):
+    """The script's body on a scene object (`args`: the parser's namespace).  filter_factory:
+    a metrics.FiltersFactory for every cloud metric (None: no filters)."""
     from raynet_amd.pointcloud import get_pointcloud
     frame_idxs = [int(i) for i in np.arange(scene.n_images)[args.frame_idxs]]
     depthmaps = [os.path.join(args.predictions_directory, args.predicted_files_format % (i,))
@@ -122,8 +125,8 @@ def run(scene, args):
         os.path.join(args.output_directory, "predicted_pc_s_%d.ply" % (args.scene_idx,)))
     results = {}
     for name in args.metric:
-        values, _ = build_metric(name, args).compute(scene, frame_idxs, depthmaps,
-                                                     predicted_pointcloud)
+        values, _ = build_metric(name, args, filter_factory).compute(
+            scene, frame_idxs, depthmaps, predicted_pointcloud)
         results[name] = values
         print(name, " mean: ", values.mean(), " median: ", np.median(values))
     return results

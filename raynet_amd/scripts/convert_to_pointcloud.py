@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Depth maps -> point cloud (the reference's raynet/scripts/convert_to_pointcloud.py:17-134).
+
+    python -m raynet_amd.scripts.convert_to_pointcloud DATASET_DIR PREDICTIONS_DIR OUTPUT_DIR
+
+reads the predicted depth maps PREDICTIONS_DIR/<pred_suffix>_%d.npy (or _%03d.npy, whichever
+the first frame has) of the chosen frames, turns them into the predicted point cloud and saves
+it as OUTPUT_DIR/predicted_pc_s_%d.ply.  With filters -- the scene's observation mask
+(VoxelMask; DTU scans have one) and --min_distance d (ReduceDensity: no two kept points within
+d; -1, the default, is off) -- the filtered cloud is saved as filtered_predicted_pc_s_%d.ply
+as well, and each filter leaves its own PLY in OUTPUT_DIR.  The flags are the reference's, with
+its defaults; --seed is new: the thinning's visiting order (the reference shuffles unseeded).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from .compute_metrics import frame_idxs_type
+
+
+def build_filter_factory(scene, min_distance, output_directory=None, seed=0):
+    """convert_to_pointcloud.py:17-27: [VoxelMask if the scene has an observation mask,
+    ReduceDensity if min_distance != -1], in this order."""
+    from raynet_amd.metrics import FiltersFactory, ReduceDensity, VoxelMask
+    filters = []
+    mask = scene.observation_mask
+    if mask is not None:
+        filters.append(VoxelMask(scene.bbox, mask, output_directory))
+    if min_distance != -1:
+        filters.append(ReduceDensity(min_distance, output_directory, seed=seed))
+    return FiltersFactory(filters)
+
+
+def find_format(input_directory, key, idx):
+    """convert_to_pointcloud.py:30-35: "<key>_%d.npy" if that file of frame idx exists, else
+    "<key>_%03d.npy"."""
+    if os.path.isfile(os.path.join(input_directory, "%s_%d.npy" % (key, idx))):
+        return key + "_%d.npy"
+    return key + "_%03d.npy"
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Transform the input depth maps to a pointcloud")
+    p.add_argument("dataset_directory", help="The dataset to load")
+    p.add_argument("predictions_directory", help="The directory containing the model's predictions")
+    p.add_argument("output_directory", help="The directory to save the predicted point cloud")
+    p.add_argument("--scene_idx", type=int, default=0, help="DTU: the scan number")
+    p.add_argument("--frame_idxs", type=frame_idxs_type, default=":",
+                   help="Choose the frames that correspond to the ordered prediction files")
+    p.add_argument("--pred_suffix", default="depth",
+                   help="The suffix for the predicted files (default=depth)")
+    # scripts/arguments.py:300-330 (dataset)
+    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
+                   default="filesystem")
+    p.add_argument("--illumination_condition", default="max")
+    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
+    # :259-297 (metrics)
+    p.add_argument("--borders", default=40, type=int,
+                   help="The number of pixels to drop from the borders of the image")
+    p.add_argument("--truncate", default=float("inf"), type=float,
+                   help="Truncate all distances to this number if they are larger")
+    p.add_argument("--min_distance", default=-1, type=float,
+                   help="Reduce the density of the points based on this distance")
+    p.add_argument("--consistency_threshold", default=0.75, type=float)
+    p.add_argument("--n_neighbors", default=5, type=int,
+                   help="Number of views considered during the consistency check")
+    p.add_argument("--with_consistency_check", action="store_true")
+    p.add_argument("--seed", default=0, type=int,
+                   help="--min_distance: the seed of the thinning's visiting order")
+    return p
+
+
+def main(argv=None):
+    """-> (predicted cloud, filtered cloud or None), after writing the PLY files."""
+    args = build_parser().parse_args(argv)
+    if isinstance(args.frame_idxs, str):
+        args.frame_idxs = frame_idxs_type(args.frame_idxs)
+    from raynet_amd.common.scene import get_scene
+    if args.dataset_type == "dtu":
+        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
+                          illumination=args.illumination_condition,
+                          select_neighbors_based_on=args.select_neighbors_based_on)
+    else:
+        scene = get_scene("restrepo", args.dataset_directory,
+                          select_neighbors_based_on=args.select_neighbors_based_on)
+    return run(scene, args)
+
+
+def run(scene, args):
+    """The script's body on a scene object (`args`: the parser's namespace)."""
+    from raynet_amd.pointcloud import get_pointcloud
+    frame_idxs = [int(i) for i in np.arange(scene.n_images)[args.frame_idxs]]
+    os.makedirs(args.output_directory, exist_ok=True)
+    filter_factory = build_filter_factory(scene, args.min_distance,
+                                          output_directory=args.output_directory, seed=args.seed)
+    fmt = find_format(args.predictions_directory, args.pred_suffix, frame_idxs[0])
+    depthmaps = [os.path.join(args.predictions_directory, fmt % (i,)) for i in frame_idxs]
+    predicted_pointcloud = get_pointcloud(
+        scene, frame_idxs, depthmaps, args.with_consistency_check, borders=args.borders,
+        consistency_threshold=args.consistency_threshold, n_neighbors=args.n_neighbors)
+    print("Saving predicted point-cloud for scene %d ..." % (args.scene_idx,))
+    predicted_pointcloud.save_ply(
+        os.path.join(args.output_directory, "predicted_pc_s_%d.ply" % (args.scene_idx,)))
+    unfiltered = predicted_pointcloud.points
+    if not filter_factory.has_filters:
+        return unfiltered, None
+    predicted_pointcloud.filter(filter_factory)
+    predicted_pointcloud.save_ply(
+        os.path.join(args.output_directory, "filtered_predicted_pc_s_%d.ply" % (args.scene_idx,)))
+    return unfiltered, predicted_pointcloud.points
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

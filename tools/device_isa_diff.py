@@ -8,8 +8,10 @@ only, no GPU needed; about a minute each, side by side) and compares, kernel by 
 instruction text and the .amdhsa_kernel descriptor (VGPRs, SGPRs, LDS, scratch).  Two things
 differ between any two sources and are replaced first: the __hip_cuid_<hash> symbol (a hash of
 the source text) and the function index in local labels (.LBB<k>_<n> and the comments that cite
-them, .Lfunc_begin<k>, .Lfunc_end<k>: moving code between files renumbers functions).  Prints
+them, .Lfunc_begin<k>, .Lfunc_end<k>: moving code between files renumbers functions; the blanks
+in front of a comment, which pad it to a column, go with them).  Prints
 the kernel count and `identical` or the first kernel that differs; the exit status is non-zero on a difference.
+Kernels only B has (a feature's new ones) are listed and are no difference; a kernel only A has is one.
 """
 import os
 import re
@@ -23,7 +25,9 @@ sys.path.insert(0, REPO)
 
 VOLATILE = [(re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_X"),
             (re.compile(r"(?:(?<=\.L)|\b)BB\d+_"), "BBk_"),      # .LBB<k>_<n>, and BB<k>_<n> in loop comments
-            (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1k")]
+            (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1k"),
+            # a label's trailing comment is padded to a column: one more digit in <k> moves it
+            (re.compile(r"[ \t]+;"), " ;")]
 
 
 def compile_isa(csrc, out, extra=()):
@@ -53,9 +57,9 @@ def kernels(path):
 
 def compare(a, b):
     """(kernel count of a, None) or (count, what differs first)"""
-    if set(a) != set(b):
-        only = sorted(set(a) ^ set(b))
-        return len(a), "kernel sets differ (%d vs %d), e.g. %s" % (len(a), len(b), only[0])
+    if set(a) - set(b):
+        only = sorted(set(a) - set(b))
+        return len(a), "%d kernels of A are missing in B, e.g. %s" % (len(only), only[0])
     for name in sorted(a):
         for what, x, y in zip(("instructions", "descriptor"), a[name], b[name]):
             if x != y:
@@ -74,8 +78,12 @@ def main(argv):
         with ThreadPoolExecutor(2) as pool:
             fa = pool.submit(compile_isa, a_csrc, os.path.join(tmp, "a.s"), extra)
             fb = pool.submit(compile_isa, b_csrc, os.path.join(tmp, "b.s"), extra)
-            count, diff = compare(kernels(fa.result()), kernels(fb.result()))
+            ka, kb = kernels(fa.result()), kernels(fb.result())
+            count, diff = compare(ka, kb)
     label = " ".join(extra) or "default build"
+    added = sorted(set(kb) - set(ka))
+    if added:
+        print("%s: %d kernels only in B: %s" % (label, len(added), " ".join(added)))
     if diff:
         print("%s: %d kernels, DIFFERENT: %s" % (label, count, diff))
         return 1
