@@ -628,6 +628,31 @@ int rn_thin_round(rn_ctx *ctx, int32_t n_work, const int32_t *work, int32_t n,
                   const int32_t *index, double r2, int32_t *state, int32_t *undecided,
                   void *stream);
 
+/* ---- ground-truth depth from a point cloud ----------------
+ * A DTU scan ships its ground truth as one point cloud; its depth maps are the cloud's
+ * z-buffer in every view (no counterpart in the reference, which reads the maps from disk). */
+
+/* points [n_points][3] f32, cameras [n_views][21] f64 (K [3][3] | R [3][3] | t [3], row-major),
+ * all device memory.  Per point and view, in float64 with every operation rounded on its own:
+ *     Xc_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k,   h_k = (K_k0 Xc_0 + K_k1 Xc_1) + K_k2 Xc_2,
+ *     (iu, iv) = (rint(h_0 / h_2), rint(h_1 / h_2))   (half to even),   z32 = (float) Xc_2;
+ * the point counts iff 0 < h_2 < inf, Xc_2 > 0, z32 < inf, 0 <= iu < W and 0 <= iv < H (a NaN
+ * fails every test).  zbuf [n_views][H][W] u32: zbuf[view][iv][iu] = min(itself, bit pattern of
+ * z32) -- an unsigned minimum, which for positive floats is the float minimum.  THE CALLER
+ * fills zbuf with 0x7F800000 (+inf) before the first call; the entry never clears it, so
+ * several calls accumulate several chunks of a cloud into one buffer.  All views are one
+ * launch: a point is read once.  n_points <= 2^30; n_points == 0 or n_views == 0 is an empty
+ * launch. */
+int rn_cloud_zbuffer(rn_ctx *ctx, int32_t n_points, const float *points, int32_t n_views,
+                     const double *cameras, int32_t H, int32_t W, uint32_t *zbuf, void *stream);
+
+/* The same buffer, and counts [2] u64 (device, zeroed by the caller) += the (point, view) pairs
+ * that landed on a pixel | those of them whose atomic the pre-test skipped (the stored value was
+ * already <= z32): the measurement of tools/cloud_depth_bench.py. */
+int rn_cloud_zbuffer_counted(rn_ctx *ctx, int32_t n_points, const float *points, int32_t n_views,
+                             const double *cameras, int32_t H, int32_t W, uint32_t *zbuf,
+                             uint64_t *counts, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

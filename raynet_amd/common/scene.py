@@ -296,7 +296,8 @@ class DTUScene(Scene):
     """A scan of the DTU MVS dataset (scene.py:257-452): Rectified/scanNNN images of one
     illumination, SampleSet/MVS_Data/Calibration/cal18 {intrinsic.txt, pos_*.txt},
     ObsMask%d_10.mat (bbox), Depth/scanNNN/*.npy (z-depth maps, converted to distances from
-    the camera centre like the reference does)."""
+    the camera centre like the reference does).  A scan without depth files gets them from its
+    point cloud Points/stl/stlNNN_total.ply, rendered on the GPU (get_gt_depth_map)."""
 
     def __init__(self, basepath, scene_idx, illumination="max",
                  select_neighbors_based_on="filesystem"):
@@ -321,6 +322,11 @@ class DTUScene(Scene):
         self._cache_depth_maps = [None] * len(self._image_paths)
         self._gt_stl_path = os.path.join(basepath, "Points", "stl",
                                          "stl%03d_total.ply" % (scene_idx,))
+        self._depth_dir = os.path.join(basepath, depth_dir)
+        self._cache_gt_depth_maps = [None] * len(self._image_paths)
+        self._cloud_renderer = None
+        # closing_radius / slope_gain / tau_px of the rendered maps (cloud_depth.depth_maps)
+        self._cloud_depth_options = {}
 
     n_images = property(lambda self: len(self._image_paths))
 
@@ -351,8 +357,39 @@ class DTUScene(Scene):
             self._cache[i] = Image.from_file(self._image_paths[i], self._read_camera_poses(i))
         return self._cache[i]
 
+    def get_gt_depth_file(self, i):
+        """The i-th sorted file of Depth/scanNNN (the reference pairs files and frames by
+        position, scene.py:277-285), None if there is none."""
+        n = len(self._depth_map_paths)
+        return self._depth_map_paths[i] if -n <= i < n else None
+
+    def _get_cloud_renderer(self):
+        """The scan's STL cloud on the GPU (cloud_depth.CloudDepthRenderer), built once."""
+        if self._cloud_renderer is None:
+            from ..cloud_depth import CloudDepthRenderer
+            from .mesh_io import parse_stl_file_to_pointcloud
+            self._cloud_renderer = CloudDepthRenderer(
+                parse_stl_file_to_pointcloud(self._gt_stl_path))
+        return self._cloud_renderer
+
     def get_gt_depth_map(self, i):
-        return np.load(self._depth_map_paths[i])
+        """[H, W] f32 z-depth map of frame i, 0 = no ground truth: the file of Depth/scanNNN
+        where there is one for the frame, else the scan's point cloud
+        (Points/stl/stlNNN_total.ply) rendered on the GPU (the cloud is
+        loaded once, a rendered map is kept per frame)."""
+        f = self.get_gt_depth_file(i)
+        if f is not None:
+            return np.load(f)
+        if self._cache_gt_depth_maps[i] is None:
+            if not os.path.isfile(self._gt_stl_path):
+                raise FileNotFoundError(
+                    "no ground-truth depth for frame %d: neither a depth map in %s nor the "
+                    "point cloud %s" % (i, self._depth_dir, self._gt_stl_path))
+            image = self.get_image(i)
+            self._cache_gt_depth_maps[i] = self._get_cloud_renderer().depth_maps(
+                [image.camera], image.height, image.width,
+                **self._cloud_depth_options)[0].cpu().numpy()
+        return self._cache_gt_depth_maps[i]
 
     def get_depth_map(self, i):
         """scene.py:372-407: per-pixel distance to the camera centre from the z-depth map."""

@@ -1129,3 +1129,6 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 
 // point-cloud filters: VoxelMask and the exact parallel ReduceDensity
 #include "raynet_filters.inl"
+
+// ground-truth depth of a point cloud: every view's z-buffer in one pass
+#include "raynet_cloud.inl"

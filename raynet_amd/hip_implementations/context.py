@@ -396,6 +396,31 @@ class HipContext(object):
                                            _ptr(points), _ptr(priority), _ptr(index), float(r2),
                                            _ptr(state), _ptr(undecided), _stream()))
 
+    # ---- ground-truth depth from a point cloud (raynet_amd/cloud_depth.py) ---------------
+    def cloud_zbuffer(self, points, cameras, H, W, zbuf, counts=None):
+        """points (n, 3) f32, cameras (V, 21) f64 (K | R | t), zbuf (V, H, W) i32 holding float
+        bit patterns, filled with 0x7F800000 by the caller; counts: None or [2] i64, zeroed
+        (landed pairs | atomics the pre-test skipped)."""
+        n, V, H, W = points.shape[0], cameras.shape[0], int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError("H, W: at least 1, got %d, %d" % (H, W))
+        if n > (1 << 30):
+            raise ValueError("points: at most 2^30 per call, got %d" % n)
+        _chk(points, torch.float32, 3 * n, "points")
+        _chk(cameras, torch.float64, 21 * V, "cameras", align=8)
+        _chk(zbuf, torch.int32, V * H * W, "zbuf")
+        if tuple(points.shape) != (n, 3) or tuple(cameras.shape) != (V, 21):
+            raise ValueError("points (n, 3) and cameras (V, 21): got %s, %s"
+                             % (tuple(points.shape), tuple(cameras.shape)))
+        if counts is None:
+            self._check(self.lib.rn_cloud_zbuffer(self._h, n, _ptr(points), V, _ptr(cameras), H, W,
+                                                  _ptr(zbuf), _stream()))
+        else:
+            _chk(counts, torch.int64, 2, "counts", align=8)
+            self._check(self.lib.rn_cloud_zbuffer_counted(self._h, n, _ptr(points), V,
+                                                          _ptr(cameras), H, W, _ptr(zbuf),
+                                                          _ptr(counts), _stream()))
+
     KERNEL_NAMES = {1: "traverse", 2: "sweep_map", 3: "bp", 4: "depth", 5: "acc", 6: "other", 7: "scatter"}
 
     # ---- ground truth from scene meshes (raynet_amd/mesh.py) ----------------------------
