@@ -339,6 +339,22 @@ int rn_scene_depth(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
                    const float *camera_center, int32_t rays_per_center, float *S_new,
                    float *depth_map, void *stream);
 
+/* The same sweep -- depth_map, S_new bit for bit as rn_scene_depth writes them -- that also
+ * keeps three numbers of every ray's depth distribution before it is thrown away.  For a ray
+ * with count > 1 voxels let d_i be the distribution (the row S_new gets) and
+ * t_i = |centre(voxel_i) - camera_centre| in fp32, the arithmetic of the depth itself:
+ *   plane 0  confidence      d_{i*}, i* the reported (first) arg-max: max_i d_i
+ *   plane 1  expected depth  mu = sum_i d_i t_i
+ *   plane 2  depth std       sqrt(max(0, sum_i d_i (t_i - mu)^2))
+ * Rays with count <= 1 send no message and their row is all zero: confidence 0, expected depth
+ * = the value depth_map gets, std 0.  stats[plane * stats_stride + ray], stats_stride >= n.
+ * depth_map, camera_center and stats are required (stats == NULL is RN_ERR_INVALID, there is
+ * no fallback to rn_scene_depth). */
+int rn_scene_depth_stats(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
+                         const int32_t *rvc, const float *acc, const float *msgs,
+                         const float *camera_center, int32_t rays_per_center, float *S_new,
+                         float *depth_map, float *stats, int64_t stats_stride, void *stream);
+
 /* ---- one pass as a PLAN (what RayNetForwardPass.forward_pass enqueues per step) ----------
  * forward_pass.py:579-748 in the resident form: the caller describes the scene's buffers once
  * and then runs whole phases of a pass with one call each -- the K1 prefix of all images, one BP
@@ -386,6 +402,17 @@ typedef struct {
                                       groups of this many RAYS per XCD, the groups dealt round the
                                       8 XCDs -- one group is what an XCD's private L2 sees side by
                                       side (a multiple of 4; 0: the library's default, 2048)    */
+    /* depth statistics (rn_scene_depth_stats), all optional: with NULL the depth sweeps are the
+       launches they are without these fields.  They go where the depths go -- */
+    float *stats;                  /* ... in row order, the counterpart of `depth`:
+                                      [3][n_images*rows_per_image], plane p of row r at
+                                      stats[p*n_images*rows_per_image + r] (used when depth_image
+                                      is NULL)                                                   */
+    float *stats_image;            /* ... in pixel order, the counterpart of `depth_image` (which it
+                                      needs): plane p of image g at stats_image[p*stats_image_stride
+                                      + g*depth_image_stride + ray_idxs[row]]; entries no ray maps
+                                      to are left as they are                                    */
+    int64_t stats_image_stride;    /* floats between two planes (>= n_images*depth_image_stride) */
 } rn_scene_plan;
 typedef enum {
     RN_RUN_PREPARE = 1,   /* traversal + plane sweep + mapping of all images (rn_scene_prepare_all) */

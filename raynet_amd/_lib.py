@@ -98,6 +98,9 @@ class ScenePlan(ctypes.Structure):
         ("depth", ctypes.c_void_p), ("prior", ctypes.c_float), ("row_layout", ctypes.c_int32),
         ("depth_image", ctypes.c_void_p), ("depth_image_stride", ctypes.c_int64),
         ("sweep_xcd_chunk", ctypes.c_int32),
+        # depth statistics (appended: the offsets above are the ones they always were)
+        ("stats", ctypes.c_void_p), ("stats_image", ctypes.c_void_p),
+        ("stats_image_stride", ctypes.c_int64),
     ]
 
 
@@ -158,6 +161,7 @@ SIGNATURES = {
     "rn_acc_reduce_local": [_P, _P, _P, _P],
     "rn_acc_add_prior": [_P, _P, _F, _P],
     "rn_scene_depth": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "rn_scene_depth_stats": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P],
     "rn_prof_begin": [_P, _I],
     "rn_prof_select": [_P, ctypes.c_uint32],
     "rn_prof_end": [_P, ctypes.POINTER(_I), _P, _P, _P],

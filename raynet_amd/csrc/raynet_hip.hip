@@ -914,6 +914,26 @@ int rn_scene_depth(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
                                      depth_map, S(stream), rays_per_center);
 }
 
+int rn_scene_depth_stats(rn_ctx *ctx, int32_t n, const float *Sr, const int32_t *vox,
+                         const int32_t *rvc, const float *acc, const float *msgs,
+                         const float *camera_center, int32_t rays_per_center, float *S_new,
+                         float *depth_map, float *stats, int64_t stats_stride, void *stream) {
+    // (before the empty-launch shortcut: asking for statistics without a place for them is an
+    // error at any n, never a plain depth sweep)
+    if (ctx && !stats) return fail(ctx, RN_ERR_INVALID, "rn_scene_depth_stats: stats is required");
+    RN_OPEN(ctx, n, all_set(Sr, vox, rvc, acc, msgs, depth_map, camera_center));
+    if (rays_per_center < 0 || stats_stride < n)
+        return fail(ctx, RN_ERR_INVALID, "rn_scene_depth_stats: bad rays_per_center or stats_stride");
+    int rc = need_axes(ctx);
+    if (rc) return rc;
+    DepthStats out;
+    out.planes = stats;
+    out.stride = stats_stride;
+    return launch_depth<true, false>(ctx, n, Sr, vox, rvc, acc, msgs, camera_center, S_new,
+                                     depth_map, S(stream), rays_per_center, AccMode(), 4,
+                                     DepthDest(), out);
+}
+
 int rn_scene_run(rn_ctx *ctx, const rn_scene_plan *pl, int32_t phases, int32_t iteration,
                  int32_t image, void *stream) {
     if (!ctx || !pl || pl->n_images < 1 || pl->n < 0 || pl->rows_per_image < pl->n ||
@@ -921,7 +941,10 @@ int rn_scene_run(rn_ctx *ctx, const rn_scene_plan *pl, int32_t phases, int32_t i
         (!(phases & RN_RUN_DEPTH_RANGE) && image >= pl->n_images) ||
         (!pl->ray_idxs && pl->n) || !pl->features_views || !pl->cameras || !pl->vox || !pl->rvc || !pl->Sr || !pl->msgs ||
         !pl->acc[0] || !pl->acc[1] || !pl->depth ||
-        (pl->depth_image && pl->depth_image_stride < 1) || pl->sweep_xcd_chunk < 0 ||
+        (pl->depth_image && pl->depth_image_stride < 1) ||
+        (pl->stats_image && (!pl->depth_image ||
+                             pl->stats_image_stride < pl->n_images * pl->depth_image_stride)) ||
+        pl->sweep_xcd_chunk < 0 ||
         pl->sweep_xcd_chunk % 4 ||
         (phases & ~(RN_RUN_PREPARE | RN_RUN_SWEEP | RN_RUN_COMBINE | RN_RUN_DEPTH | RN_RUN_DEPTH_RANGE)) ||
         ((phases & RN_RUN_DEPTH_RANGE) &&
@@ -996,24 +1019,35 @@ int rn_scene_run(rn_ctx *ctx, const rn_scene_plan *pl, int32_t phases, int32_t i
             return pl->depth_image ? pl->depth_image + (size_t)first * pl->depth_image_stride
                                    : pl->depth + (size_t)first * pl->rows_per_image;
         };
+        // the statistics go where the depths go: pixel order next to depth_image, else row order
+        auto stats = [&](int first) {
+            DepthStats s;
+            if (pl->depth_image ? pl->stats_image != nullptr : pl->stats != nullptr) {
+                s.planes = pl->depth_image ? pl->stats_image + (size_t)first * pl->depth_image_stride
+                                           : pl->stats + (size_t)first * pl->rows_per_image;
+                s.stride = pl->depth_image ? pl->stats_image_stride : rows;
+            }
+            return s;
+        };
         if (image < 0)
             return launch_depth<true, false>(ctx, (int)rows, pl->Sr, pl->vox, pl->rvc, acc, pl->msgs, cc,
                                              nullptr, out(0), st, (int)pl->rows_per_image, am,
-                                             cam_stride, dest);
+                                             cam_stride, dest, stats(0));
         if (phases & RN_RUN_DEPTH_RANGE) {
             const int first = image & 0xffff, count = image >> 16;
             const size_t r0 = (size_t)first * pl->rows_per_image;
             return launch_depth<true, false>(ctx, (int)(count * pl->rows_per_image), pl->Sr + r0 * M,
                                              pl->vox + r0 * M, pl->rvc + r0, acc, pl->msgs + r0 * M,
                                              cc + (size_t)first * cam_stride, nullptr, out(first),
-                                             st, (int)pl->rows_per_image, am, cam_stride, dest);
+                                             st, (int)pl->rows_per_image, am, cam_stride, dest,
+                                             stats(first));
         }
         const size_t row0 = (size_t)image * pl->rows_per_image;
         // (one image: a single group of rows_per_image >= n rows)
         return launch_depth<true, false>(ctx, pl->n, pl->Sr + row0 * M, pl->vox + row0 * M,
                                          pl->rvc + row0, acc, pl->msgs + row0 * M,
                                          cc + (size_t)image * cam_stride, nullptr, out(image),
-                                         st, 0, am, 4, dest);
+                                         st, 0, am, 4, dest, stats(image));
     }
     return RN_OK;
 }

@@ -406,16 +406,40 @@ int launch_bp(rn_ctx *ctx, int n, const float *Sv, const int32_t *vox, const int
     return RN_OK;
 }
 
+// the statistics planes of a depth sweep (k_depth_stats), indexed as its depth map is; none: k_depth
+struct DepthStats {
+    float *planes = nullptr;
+    int64_t stride = 0;
+};
 template <bool PACKED, bool CLIP_IN>
 int launch_depth(rn_ctx *ctx, int n, const float *Sv, const int32_t *vox, const int32_t *rvc,
                  const float *acc, const float *msgs, const float *cc, float *S_new,
                  float *depth_map, hipStream_t st, int rays_per_center = 0,
                  const AccMode &am = AccMode(), int cc_stride = 4,
-                 const DepthDest &dest = DepthDest()) {
+                 const DepthDest &dest = DepthDest(), const DepthStats &stats = DepthStats()) {
     ProfScope prof(ctx, RN_K_DEPTH, n, st);
     // (k_depth's STEADY form -- its flags known at compile time, as k_bp's: slower with plain
     // row loads, 0.746 -> 0.772 ms per step, faster with the non-temporal ones, 0.717 -> 0.699)
     const bool steady = PACKED && !CLIP_IN && msgs && !S_new && depth_map && am.biased;
+    if constexpr (PACKED && !CLIP_IN) {
+        if (stats.planes) {
+            if (!depth_map || !cc)
+                return fail(ctx, RN_ERR_INVALID, "depth statistics need the depth map and the camera centre");
+            with_chunks((ctx->p.M + WAVE - 1) / WAVE, [&](auto nch) {
+                with_bool(steady, [&](auto sy) {
+                    hipLaunchKernelGGL((k_depth_stats<decltype(nch)::value, CLIP_IN, decltype(sy)::value>),
+                                       dim3(ray_blocks_mrf(n)), dim3(RAY_BLOCK), 0, st, ctx->p, n, Sv,
+                                       vox, rvc, acc, msgs, ctx->axes, cc, S_new, depth_map,
+                                       rays_per_center, am.bias, am.biased ? 1 : 0, cc_stride, dest,
+                                       stats.planes, stats.stride);
+                });
+            });
+            RN_LAUNCH_CHECK(ctx);
+            return RN_OK;
+        }
+    } else if (stats.planes) {
+        return fail(ctx, RN_ERR_INVALID, "depth statistics: resident (packed, clipped) rows only");
+    }
     with_chunks((ctx->p.M + WAVE - 1) / WAVE, [&](auto nch) {
         with_bool(steady, [&](auto sy) {
             hipLaunchKernelGGL((k_depth<decltype(nch)::value, PACKED, CLIP_IN, decltype(sy)::value>),

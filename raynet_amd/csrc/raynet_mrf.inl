@@ -868,16 +868,41 @@ __global__ void k_acc_combine_fixed(unsigned long long *part, int64_t G, float p
 
 // ------------------------------------------------- K4 / K2 tail: depth estimate
 // Writes the distribution (if S_new) and/or the arg-max depth (if depth_map).
+// distance of a packed voxel's centre from the camera centre, the arithmetic of k_depth's tail
+__device__ __forceinline__ float voxel_distance(const Params &p, const float *__restrict__ axes,
+                                                const float *__restrict__ cc, int pk) {
+    const float pt[3] = {axes[pk >> 20], axes[p.gx + ((pk >> 10) & 1023)],
+                         axes[p.gx + p.gy + (pk & 1023)]};
+    float sum = 0.0f;
+    for (int i = 0; i < 3; i++) {
+        const float d = pt[i] - cc[i];
+        sum += d * d;
+    }
+    return sqrtf(sum);
+}
+// What the STATS bodies keep of the distribution besides its arg-max (include/raynet_hip.h,
+// rn_scene_depth_stats): the lane's share of the shifted moments sum d (t - pivot) and
+// sum d (t - pivot)^2, t the distance of a voxel's centre from the camera, pivot = t of the
+// ray's first voxel (wave-uniform).  One pass, in the loop that has d in a register anyway:
+// a second pass would keep a t per chunk alive in bodies that sit at ~100 VGPRs without it.
+// `top`: the distribution's maximum as the arg-max found it.  The plain bodies get no object at
+// all (the default null pointer; a reference to an empty one already moved their registers about).
+struct DepthMoments {
+    const float *axes = nullptr, *cc = nullptr;
+    float pivot = 0.0f, m1 = 0.0f, m2 = 0.0f, top = 0.0f;
+};
 // depth distribution of one ray with NB >= ceil(count / 64) chunks (mrf_bp.cu:37-86);
 // returns the lane's best (value, index) for the arg-max
 // (STEADY: the plan path's depth sweep -- messages exist, sums + prior, no distribution written)
-template <int NB, bool PACKED, bool CLIP_IN, bool STEADY = false>
+// (STATS: the lane's share of the distribution's moments goes to *mom, see DepthMoments)
+template <int NB, bool PACKED, bool CLIP_IN, bool STEADY = false, bool STATS = false>
 __device__ __forceinline__ void depth_ray(const Params &p, int r, int count, int lane,
                                           const float *__restrict__ S,
                                           const int32_t *__restrict__ vox,
                                           const float *__restrict__ acc,
                                           const float *__restrict__ msgs, float *S_new, float &best,
-                                          int &best_i, int &best_pk, float acc_bias, bool biased) {
+                                          int &best_i, int &best_pk, float acc_bias, bool biased,
+                                          DepthMoments *mom = nullptr) {
     if (STEADY) {
         biased = true;
         S_new = nullptr;
@@ -934,6 +959,15 @@ __device__ __forceinline__ void depth_ray(const Params &p, int r, int count, int
                 best = d;
                 best_i = i;
                 best_pk = cur.pk[ch];     // (its voxel word: no second trip to the list)
+            }
+            if constexpr (STATS) {
+                const float t = voxel_distance(p, mom->axes, mom->cc, cur.pk[ch]);
+                // (lane 0 of chunk 0 is the ray's first voxel and is active here: count > 1)
+                if (ch == 0)
+                    mom->pivot = __builtin_bit_cast(float, uniform(__builtin_bit_cast(int, t)));
+                const float u = t - mom->pivot, du = d * u;
+                mom->m1 += du;
+                mom->m2 += du * u;
             }
         }
     }
@@ -1020,6 +1054,96 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_depth(Params p, int n, const floa
         // row order, or the map in PIXEL order (forward_pass.py:744 hands out `.reshape(W, H).T`
         // of the ray-index-ordered vector): no reordering pass behind the sweep
         if (out_at >= 0) depth_map[out_at] = sqrtf(sum);
+    }
+}
+
+// k_depth with the statistics planes: besides the depth, lane 0 writes
+// stats[plane * stats_stride + <where the depth goes>] -- 0 confidence (the distribution's
+// maximum, the value the arg-max found), 1 expected depth, 2 standard deviation of the depth
+// (include/raynet_hip.h, rn_scene_depth_stats).  Packed lists only; depth_map and stats are
+// required.  A kernel of its own next to k_depth, whose text -- comments on the steps there --
+// is left exactly as it was: sharing the body through an inlined function was tried and moved
+// registers about in k_depth's 8-chunk STEADY body, and the plain sweep is to keep its
+// instructions (profiles/depth_stats_isa_identity.txt).
+template <int NCH, bool CLIP_IN, bool STEADY>
+__global__ __launch_bounds__(RAY_BLOCK) void k_depth_stats(Params p, int n, const float *S,
+                                                       const int32_t *__restrict__ vox,
+                                                       const int32_t *__restrict__ rvc,
+                                                       const float *__restrict__ acc,
+                                                       const float *__restrict__ msgs,
+                                                       const float *__restrict__ axes,
+                                                       const float *__restrict__ cc, float *S_new,
+                                                       float *depth_map, int rays_per_center,
+                                                       float acc_bias, int biased, int cc_stride,
+                                                       DepthDest dest, float *stats,
+                                                       int64_t stats_stride) {
+    int lane;
+    const int r = ray_of_wave<RAY_BLOCK, XCD_CHUNK_DEPTH>(n, lane);
+    if (r < 0) return;
+    const int group = rays_per_center > 0 ? r / rays_per_center : 0;
+    if (rays_per_center > 0 && cc) cc += (size_t)cc_stride * group;
+    int64_t out_at = r;
+    if (dest.pixel_of_row) {
+        const int lr = r - group * rays_per_center;
+        out_at = lr < dest.rows
+                     ? (int64_t)group * dest.image_stride + uniform(dest.pixel_of_row[lr]) : -1;
+    }
+    const int count = min(uniform(rvc[r]), p.M);
+    float best = -INFINITY;
+    int best_i = 0, best_pk = 0;
+    DepthMoments mom;
+    mom.axes = axes;
+    mom.cc = cc;
+    if (count > 1) {
+        const int nch = (count + WAVE - 1) / WAVE;
+#define RN_DE_BODY(NB) \
+    depth_ray<NB, true, CLIP_IN, STEADY, true>(p, r, count, lane, S, vox, acc, msgs, S_new, best, best_i, best_pk, \
+                                       acc_bias, biased != 0, &mom)
+        RN_DISPATCH_CHUNKS(NCH, nch, RN_DE_BODY);
+#undef RN_DE_BODY
+    } else if (S_new) {
+        for (int i = lane; i < count; i += WAVE) S_new[(size_t)r * p.M + i] = 0.0f;
+    }
+    int won_pk = -1;
+    {
+        // d of the reported voxel: the first maximum IS the maximum -- no second search
+        mom.top = wave_max(best);
+        const int mine = best_i;
+        best_i = wave_min_i(best == mom.top ? best_i : 0x7fffffff);
+        const unsigned long long who = __ballot(best == mom.top && mine == best_i);
+        if (who) won_pk = __builtin_amdgcn_readlane(best_pk, (int)__builtin_ctzll(who));
+        if (best_i == 0x7fffffff) best_i = 0;
+    }
+    if (count > 1) {                // (uniform: all lanes take part in the sums)
+        mom.m1 = wave_sum(mom.m1);
+        mom.m2 = wave_sum(mom.m2);
+    }
+    if (lane == 0 && out_at >= 0) {
+        int x = 0, y = 0, z = 0;
+        if (count > 1 && won_pk >= 0) {
+            x = won_pk >> 20; y = (won_pk >> 10) & 1023; z = won_pk & 1023;
+        } else if (count > 0) {
+            load_voxel<true>(vox + (size_t)r * p.M, count > 1 ? best_i : 0, x, y, z);
+        }
+        const float pt[3] = {axes[x], axes[p.gx + y], axes[p.gx + p.gy + z]};
+        float sum = 0.0f;
+        for (int i = 0; i < 3; i++) {
+            const float d = pt[i] - cc[i];
+            sum += d * d;
+        }
+        const float depth = sqrtf(sum);
+        depth_map[out_at] = depth;
+        // rays that send nothing (count <= 1) have an all-zero row: confidence 0, the reported
+        // depth as the mean, no spread
+        float conf = 0.0f, mean = depth, sd = 0.0f;
+        if (count > 1) {
+            conf = mom.top;
+            mean = mom.pivot + mom.m1;
+            sd = sqrtf(fmaxf(0.0f, mom.m2 - mom.m1 * mom.m1));
+        }
+        stats[out_at] = conf;
+        stats[stats_stride + out_at] = mean;
+        stats[2 * stats_stride + out_at] = sd;
     }
 }
 

@@ -126,6 +126,25 @@ def tile_order(ray_idxs, H, W, tile_x, tile_y, along_rows=False):
     return ray_idxs[torch.argsort(key)].to(torch.int32).contiguous()
 
 
+class DepthStatistics(object):
+    """What `forward_pass(..., with_statistics=True)` yields next to an image's depth map: three
+    (H, W) float32 maps in the depth map's orientation, taken from every ray's depth distribution
+    d_i over its traversed voxels (include/raynet_hip.h, rn_scene_depth_stats) --
+      confidence      d of the reported voxel, i.e. the distribution's maximum
+      expected_depth  sum d_i t_i, t_i the distance of voxel i's centre from the camera
+      depth_std       the distribution's standard deviation along the ray
+    A ray that crosses at most one voxel (and a pixel without a ray) has confidence 0 and
+    depth_std 0; its expected depth is its depth."""
+    __slots__ = ("confidence", "expected_depth", "depth_std")
+    FIELDS = __slots__
+
+    def __init__(self, confidence, expected_depth, depth_std):
+        self.confidence, self.expected_depth, self.depth_std = confidence, expected_depth, depth_std
+
+    def __iter__(self):
+        return iter((self.confidence, self.expected_depth, self.depth_std))
+
+
 def shard_bounds(n, rank, world):
     """Contiguous slice [lo, hi) of an n-long ray list owned by `rank`."""
     return (n * rank) // world, (n * (rank + 1)) // world
@@ -443,11 +462,17 @@ class RayNetForwardPass(ForwardPass):
         return float(np.float32(np.log(gamma) - np.log(1 - gamma)))
 
     # -- the generator -------------------------------------------------------
-    def forward_pass(self, scene, images_range):
+    def forward_pass(self, scene, images_range, with_statistics=False):
+        """One depth map per reference image; with_statistics: (depth map, DepthStatistics) pairs
+        -- on a rank that does not assemble an image (map_owner), (None, None)."""
         assert isinstance(images_range, tuple)
         if self.schedule == "reference":
+            if with_statistics:
+                raise ValueError(
+                    "with_statistics=True needs schedule=\"resident\": the literal K1 / K2 schedule "
+                    "decodes with the fused kernel, which does not keep the depth distribution")
             return self._forward_pass_reference(scene, images_range)
-        return self._forward_pass_resident(scene, images_range)
+        return self._forward_pass_resident(scene, images_range, bool(with_statistics))
 
     # -- the plan of a resident pass -------------------------------------------
     # Everything of a pass that depends on the scene's cameras, the image range, the options and
@@ -583,7 +608,7 @@ class RayNetForwardPass(ForwardPass):
                 free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
             free += old_bytes
             budget = 0.9 * free
-        fixed = V * per_image + 4 * G * 8 + V * npad * 48
+        fixed = V * per_image + 4 * G * 8 + V * npad * (60 if plan["with_stats"] else 48)
         if budget > 0 and fixed + 2 * per_image > budget:
             raise MemoryError(
                 "resident schedule: the messages of %d reference images (%.1f GB) do not leave "
@@ -606,6 +631,9 @@ class RayNetForwardPass(ForwardPass):
             msgs=torch.empty((V * npad, M), dtype=torch.float32, device=dev),   # see _Messages
             rvc=torch.zeros((V * npad,), dtype=torch.int32, device=dev),   # padding rays: count 0
             depth=torch.zeros((V * npad,), dtype=torch.float32, device=dev),
+            # confidence | expected depth | depth std of every row, as `depth` (with_statistics)
+            stats=(torch.zeros((3, V * npad), dtype=torch.float32, device=dev)
+                   if plan["with_stats"] else None),
             # granular path: iteration 0 reads the prior from a buffer no sweep ever writes
             acc_prior=torch.full((G,), prior, dtype=torch.float32, device=dev),
             acc_a=torch.empty((G,), dtype=torch.float32, device=dev),
@@ -613,7 +641,7 @@ class RayNetForwardPass(ForwardPass):
             acc_part=(torch.zeros((G,), dtype=torch.int64, device=dev) if fixed_pt else
                       torch.zeros((ctx.acc_copies(), G), dtype=torch.float32, device=dev)))
 
-    def _build_plan(self, scene, refs, bank, ctx, dist, rank, world):
+    def _build_plan(self, scene, refs, bank, ctx, dist, rank, world, with_stats=False):
         gp, opt = self._generation_params, self.options
         M, N = self._rows_M(), gp.neighbors + 1
         H, W = scene.image_shape
@@ -629,7 +657,7 @@ class RayNetForwardPass(ForwardPass):
         # (the allocator placed recomputed maps elsewhere) the pointer table is refreshed.
         key = (id(scene), tuple(id(c) for c in cams), tuple(sorted(views_of.items())), tuple(refs),
                H, W, M, N, gp.depth_planes, world, rank, dist is not None, opt.key(),
-               self.rays_batch, str(dev), self._prior())
+               self.rays_batch, str(dev), self._prior(), with_stats)
         plan = self._plan
         if plan is not None and plan["key"] == key and not self._filter_out_rays:
             if plan["ptrs"] != ptrs:
@@ -683,7 +711,7 @@ class RayNetForwardPass(ForwardPass):
                     cam_dev=cam_dev, views_of=views_of, lists=lists, bounds=bounds,
                     balance=balance, shards=shards, npad=npad, shared=shared,
                     patch_rows=patch_rows, fast=None, direct=False, world=world,
-                    along_rows=self._along_rows,
+                    along_rows=self._along_rows, with_stats=with_stats,
                     table=torch.tensor(ptrs, dtype=torch.int64).to(dev) if V else None)
         self._plan_buffers(ctx, plan, refs, old_bytes)
         # static views of every image's rows in the scene-wide buffers
@@ -720,11 +748,18 @@ class RayNetForwardPass(ForwardPass):
             plan["direct"] = dist is None
             if plan["direct"]:
                 plan["maps_dev"] = torch.zeros((V, H * W), dtype=torch.float32, device=dev)
+            # the statistics go where the depths go (rn_scene_plan.stats / stats_image)
+            stats_to = {}
+            if with_stats and plan["direct"]:
+                plan["stats_dev"] = torch.zeros((3, V, H * W), dtype=torch.float32, device=dev)
+                stats_to = {"stats_image": plan["stats_dev"]}
+            elif with_stats:
+                stats_to = {"stats": plan["stats"]}
             plan["fast"] = ctx.scene_plan(
                 V, npad, shards[0][0], plan["table"], cam_dev, plan["vox"], plan["rvc"],
                 plan["Sr"], plan["msgs"], plan["acc_a"], plan["acc_b"], plan["depth"],
                 plan["prior"], patch_rows, acc_fixed=plan["acc_part"] if plan["fixed"] else None,
-                **({"depth_image": plan["maps_dev"]} if plan["direct"] else {}))
+                **dict({"depth_image": plan["maps_dev"]} if plan["direct"] else {}, **stats_to))
         if not self._filter_out_rays:
             self._plan = plan
         return plan
@@ -747,11 +782,14 @@ class RayNetForwardPass(ForwardPass):
     MAX_LEASED_SETS = 4
 
     @staticmethod
-    def _new_set(V, HW, cuda):
+    def _new_set(V, HW, cuda, with_stats=False):
         # `live`: one token per array out there.  set.add / set.discard are single operations under
         # the GIL, so a finaliser running in the middle of a pass (or in another thread) cannot
         # lose an update the way a counter's read-modify-write could
+        # (the statistics maps of a pass live and are leased with its depth maps: one set)
         return dict(host=torch.empty((V, HW), dtype=torch.float32, pin_memory=cuda), live=set(),
+                    stats=(torch.empty((3, V, HW), dtype=torch.float32, pin_memory=cuda)
+                           if with_stats else None),
                     tokens=itertools.count())
 
     def _take_set(self, plan, V, HW, cuda):
@@ -763,16 +801,17 @@ class RayNetForwardPass(ForwardPass):
                 if not st["live"]:
                     return i, st, True
             if len(pool) < self.MAX_LEASED_SETS:
-                pool.append(self._new_set(V, HW, cuda))
+                pool.append(self._new_set(V, HW, cuda, plan.get("with_stats", False)))
                 return len(pool) - 1, pool[-1], True
         if plan["scratch"] is None:
-            plan["scratch"] = self._new_set(V, HW, cuda)
+            plan["scratch"] = self._new_set(V, HW, cuda, plan.get("with_stats", False))
         return -1, plan["scratch"], False
 
     @staticmethod
-    def _lease(st, k):
-        """Image k of the set as an ndarray that owns a lease on the set's memory."""
-        row = st["host"][k]
+    def _lease(st, k, plane=None):
+        """Image k of the set (plane: of its statistics plane) as an ndarray that owns a lease on
+        the set's memory."""
+        row = st["host"][k] if plane is None else st["stats"][plane, k]
         owner = (ctypes.c_float * row.numel()).from_address(row.data_ptr())
         token = next(st["tokens"])
         st["live"].add(token)
@@ -829,7 +868,11 @@ class RayNetForwardPass(ForwardPass):
                         hi_q - lo_q, dtype=torch.int64, device=dev)
                 idx[j] = at.to(torch.int32)
             table = idx.reshape(-1)
-        plan["rows"] = dict(mine=mine, recv=recv, table=table)
+        # (the statistics rows travel as the depth rows do: a block of `recv`'s shape per plane,
+        # the same table)
+        recv_stats = torch.zeros((3, world * blk + 1), dtype=torch.float32, device=dev) \
+            if plan.get("with_stats") else None
+        plan["rows"] = dict(mine=mine, recv=recv, table=table, recv_stats=recv_stats)
 
     def _mark(self, name, begin):
         """bench.py --gpus N: a pair of events around every exchange of an eager pass
@@ -839,7 +882,7 @@ class RayNetForwardPass(ForwardPass):
             ev.record()
             self.trace.append((name, begin, ev))
 
-    def _emit_direct(self, plan, groups, host_set):
+    def _emit_direct(self, plan, groups, host_set, stats_set=None):
         """The maps of the image groups [a, b) -- written in pixel order by their depth launches,
         ev_ready[a] recorded behind each -- go to the pinned host maps, one copy per group."""
         copy = self._copy_stream
@@ -847,6 +890,9 @@ class RayNetForwardPass(ForwardPass):
             for a, b in groups:
                 copy.wait_event(plan["ev_ready"][a])
                 host_set[a:b].copy_(plan["maps_dev"][a:b], non_blocking=True)
+                if stats_set is not None:
+                    for p in range(3):
+                        stats_set[p, a:b].copy_(plan["stats_dev"][p, a:b], non_blocking=True)
                 plan["ev_done"][a].record()
                 for k in range(a, b):
                     plan["wait_ev"][k] = plan["ev_done"][a]
@@ -885,7 +931,8 @@ class RayNetForwardPass(ForwardPass):
             self._mark("exchange", False)
         ctx.scene_run(fast, _lib.RN_RUN_COMBINE, it)
 
-    def _run_plan_path(self, plan, ctx, refs, dist, world, host_set, captured=False):
+    def _run_plan_path(self, plan, ctx, refs, dist, world, host_set, captured=False,
+                       stats_set=None):
         """One pass as phases of the C plan (include/raynet_hip.h, rn_scene_run): 1 + T calls
         for the K1 prefix and the T BP iterations, the exchange between them, then the depth
         sweep and the maps' way to the host.  Eager, or -- `captured` -- recorded into a HIP graph
@@ -918,7 +965,7 @@ class RayNetForwardPass(ForwardPass):
                 else:
                     ctx.scene_run(fast, _lib.RN_RUN_DEPTH, T, a)
                 plan["ev_ready"][a].record()
-            self._emit_direct(plan, groups, host_set)
+            self._emit_direct(plan, groups, host_set, stats_set)
         else:
             # sharded rays, owner-only maps (_epilogue_buffers): ONE depth launch over all of
             # this rank's rows, ONE all-gather of the ranks' rows, ONE stitch launch on an owner
@@ -937,6 +984,12 @@ class RayNetForwardPass(ForwardPass):
                     host = host_set.view(-1)
                     ctx.stitch_rows(rows["recv"], rows["table"],
                                     host[mine[0] * HW:(mine[-1] + 1) * HW])
+                if stats_set is not None:
+                    for p in range(3):
+                        dist.all_gather_into_tensor(rows["recv_stats"][p, :-1], plan["stats"][p])
+                        if mine:
+                            ctx.stitch_rows(rows["recv_stats"][p], rows["table"],
+                                            stats_set[p].view(-1)[mine[0] * HW:(mine[-1] + 1) * HW])
                 plan["ev_done"][0].record()
             for k in range(V):
                 plan["wait_ev"][k] = plan["ev_done"][0]
@@ -986,7 +1039,7 @@ class RayNetForwardPass(ForwardPass):
         return plan["passes"] >= 2 and ctx.scatter_settled()
 
     # -- the resident schedule ------------------------------------------------------------------
-    def _forward_pass_resident(self, scene, images_range):
+    def _forward_pass_resident(self, scene, images_range, with_stats=False):
         start, end, skip = images_range
         gp = self._generation_params
         H, W = scene.image_shape
@@ -1006,7 +1059,7 @@ class RayNetForwardPass(ForwardPass):
         gp_now = (gp.max_number_of_marched_voxels, gp.neighbors, gp.depth_planes, gp.gamma_mrf,
                   gp.padding)
         qkey = (id(scene), start, end, skip, id(self._model), dist is not None, rank, world,
-                self.options.key(), self.rays_batch, gp_now, self._filter_out_rays)
+                self.options.key(), self.rays_batch, gp_now, self._filter_out_rays, with_stats)
         q = self._quick
         plan = None
         if q is not None and q["key"] == qkey and q["plan"] is self._plan and self._ctx is not None:
@@ -1030,7 +1083,7 @@ class RayNetForwardPass(ForwardPass):
                 if f.device != dev or f.dtype != torch.float32 or not f.is_contiguous():
                     bank[v] = f.to(dev, torch.float32).contiguous()
                     moved = True
-            plan = self._build_plan(scene, refs, bank, ctx, dist, rank, world)
+            plan = self._build_plan(scene, refs, bank, ctx, dist, rank, world, with_stats)
             self._quick = None
             if plan["fast"] is not None and self._plan is plan and not moved and \
                     hasattr(self._model, "view_features"):
@@ -1062,7 +1115,7 @@ class RayNetForwardPass(ForwardPass):
             self._scatter_work_list(plan, ctx)
             # the pinned maps this pass writes: a set nobody holds a lease on (see _take_set)
             set_key, mset, leased = self._take_set(plan, V, H * W, dev.type == "cuda")
-            host_set = mset["host"]
+            host_set, stats_set = mset["host"], mset["stats"]
             # (a pass whose launches or exchanges are bracketed by events runs eagerly)
             eager = self.trace is not None or getattr(ctx, "prof_active", False) or \
                 self.options.capture == "off"
@@ -1074,7 +1127,8 @@ class RayNetForwardPass(ForwardPass):
                 try:
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
-                        self._run_plan_path(plan, ctx, refs, dist, world, host_set, captured=True)
+                        self._run_plan_path(plan, ctx, refs, dist, world, host_set, captured=True,
+                                            stats_set=stats_set)
                     plan["graphs"][gkey] = graph
                 except Exception as e:        # a transport / runtime that cannot be captured
                     import warnings
@@ -1090,7 +1144,7 @@ class RayNetForwardPass(ForwardPass):
                 self._acc_flat = plan["acc_b" if (T - 1) & 1 else "acc_a"]
                 self._acc_bias = 0.0 if plan["fixed"] else plan["prior"]
             else:
-                self._run_plan_path(plan, ctx, refs, dist, world, host_set)
+                self._run_plan_path(plan, ctx, refs, dist, world, host_set, stats_set=stats_set)
             self.captured = graph is not None
             plan["passes"] += 1
             for r in refs:
@@ -1101,11 +1155,18 @@ class RayNetForwardPass(ForwardPass):
             for k, r in enumerate(refs):
                 self.ref_idx = r
                 if owners is not None and owners[k] != rank:
-                    yield None             # another rank assembles this image (map_owner)
+                    # another rank assembles this image (map_owner)
+                    yield (None, None) if with_stats else None
                     continue
                 plan["wait_ev"][k].synchronize()
                 a = self._lease(mset, k) if leased else host_set[k].numpy().copy()
-                yield a.reshape(W, H).T
+                if with_stats:
+                    b = [self._lease(mset, k, p) if leased else stats_set[p, k].numpy().copy()
+                         for p in range(3)]
+                    yield a.reshape(W, H).T, DepthStatistics(*[m.reshape(W, H).T for m in b])
+                    del b
+                else:
+                    yield a.reshape(W, H).T
                 del a
             self._pass_complete = True
             return
@@ -1227,6 +1288,25 @@ class RayNetForwardPass(ForwardPass):
 
         n_all = V * npad
         depth_all = plan["depth"]
+        with_stats, stats_all = plan["with_stats"], plan["stats"]
+        if with_stats and not hasattr(ctx, "scene_depth_stats"):
+            raise _lib.RaynetHipError("this back end has no depth statistics (rn_scene_depth_stats)")
+
+        def depth_sweep(Sr, vox, rvc, msgs, center, dst, row0, rays_per_center=0):
+            """The depth sweep of rows [row0, row0 + len(rvc)) of the scene-wide buffers."""
+            if with_stats:
+                ctx.scene_depth_stats(Sr, vox, rvc, acc_in, msgs, center, None, dst, stats_all,
+                                      rays_per_center=rays_per_center, stats_offset=row0)
+            else:
+                ctx.scene_depth(Sr, vox, rvc, acc_in, msgs, center, None, dst,
+                                rays_per_center=rays_per_center)
+
+        def stats_to_host(r, row0, n):
+            """[(host map, event)] of image r's three statistics planes, or None"""
+            if not with_stats:
+                return None
+            return [to_host(stats_all[p, row0:row0 + n], r) for p in range(3)]
+
         pending = []
         if not collective:
             if cuda and self._side_stream is None:
@@ -1234,6 +1314,8 @@ class RayNetForwardPass(ForwardPass):
             side = self._side_stream if cuda else None
             if side is not None:
                 depth_all.record_stream(side)
+                if with_stats:
+                    stats_all.record_stream(side)
             last = per_image[refs[-1]] if refs else None
             for group in groups:
                 if not one_group:
@@ -1249,25 +1331,27 @@ class RayNetForwardPass(ForwardPass):
                     B = self.rays_batch // 256 * 256 if self.rays_batch and self.rays_batch >= 256 \
                         else max(st["n"], 1)
                     for i in range(0, st["n"], B):
-                        ctx.scene_depth(Sr_k[i:i + B], vox_k[i:i + B], st["rvc"][i:i + B],
-                                        acc_in, msgs[i:i + B], st["center"], None, dst[i:i + B])
+                        depth_sweep(Sr_k[i:i + B], vox_k[i:i + B], st["rvc"][i:i + B],
+                                    msgs[i:i + B], st["center"], dst[i:i + B], st["row0"] + i)
                     if side is None:
-                        pending.append((r,) + to_host(dst, r))
+                        pending.append((r,) + to_host(dst, r) +
+                                       (stats_to_host(r, st["row0"], st["n"]),))
                     else:
                         ready = torch.cuda.Event()
                         ready.record()
                         with torch.cuda.stream(side):
                             side.wait_event(ready)
-                            pending.append((r,) + to_host(dst, r))
+                            pending.append((r,) + to_host(dst, r) +
+                                           (stats_to_host(r, st["row0"], st["n"]),))
         else:
             centers = cam_dev[:, 12 * N + 12:].contiguous()
             for group in groups:
                 if not one_group:
                     prepare(group)
                 g0, n_g = group[0], len(group) * npad
-                ctx.scene_depth(Sr_g[:n_g], vox_g[:n_g], rvc_all[g0 * npad:g0 * npad + n_g], acc_in,
-                                msgs_all[g0 * npad:g0 * npad + n_g], centers[g0:g0 + len(group)],
-                                None, depth_all[g0 * npad:g0 * npad + n_g], rays_per_center=npad)
+                depth_sweep(Sr_g[:n_g], vox_g[:n_g], rvc_all[g0 * npad:g0 * npad + n_g],
+                            msgs_all[g0 * npad:g0 * npad + n_g], centers[g0:g0 + len(group)],
+                            depth_all[g0 * npad:g0 * npad + n_g], g0 * npad, rays_per_center=npad)
             # ONE all-gather of the ranks' row blocks (each rank sends only its own rows), ONE
             # gather that puts every image's rows of every rank into pixel order (its index
             # map depends on the ray lists and the sharding only: built once), ONE copy to the
@@ -1295,22 +1379,45 @@ class RayNetForwardPass(ForwardPass):
             done = torch.cuda.Event() if cuda else None
             if done is not None:
                 done.record()
+            stats_host = None
+            if with_stats:
+                # the three planes the same way: an all-gather and a gather each, one copy
+                if plan.get("gathered_stats") is None:
+                    plan["gathered_stats"] = torch.zeros((3, world * n_all + 1), dtype=torch.float32,
+                                                         device=dev)
+                stats_host = torch.empty((3, V * HW), dtype=torch.float32, pin_memory=cuda)
+                for p in range(3):
+                    dist.all_gather_into_tensor(plan["gathered_stats"][p, :-1], stats_all[p])
+                    stats_host[p].copy_(plan["gathered_stats"][p].index_select(0, plan["stitch_all"]),
+                                        non_blocking=True)
+                if done is not None:
+                    done = torch.cuda.Event()
+                    done.record()
             for k, r in enumerate(refs):
-                pending.append((r, host[k * HW:(k + 1) * HW], done if k == 0 else None))
+                pending.append((r, host[k * HW:(k + 1) * HW], done if k == 0 else None,
+                                None if stats_host is None else
+                                [(stats_host[p, k * HW:(k + 1) * HW], None) for p in range(3)]))
         for r in refs:
             st = per_image[r]
             self.messages.put(r, st["msgs"], st["rvc"])
             self.voxel_count[r] = st["rvc"]
         # with a process group, image k's map is handed out by ONE rank (map_owner; this
         # launch-by-launch path still moves every map to every rank: it is the fallback)
-        for k, (r, host, done) in enumerate(pending):
+        for k, (r, host, done, stats) in enumerate(pending):
             if done is not None:
                 done.synchronize()
+            for _, ev in stats or ():
+                if ev is not None:
+                    ev.synchronize()
             self.ref_idx = r
             if collective and map_owner(k, V, world) != rank:
-                yield None
+                yield (None, None) if with_stats else None
                 continue
-            yield host.numpy().reshape(W, H).T
+            if with_stats:
+                yield host.numpy().reshape(W, H).T, DepthStatistics(
+                    *[m.numpy().reshape(W, H).T for m, _ in stats])
+            else:
+                yield host.numpy().reshape(W, H).T
 
     def _forward_pass_reference(self, scene, images_range):
         """Literal schedule of forward_pass.py:579-748 with K1 / K2 (single rank)."""

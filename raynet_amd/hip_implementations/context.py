@@ -665,10 +665,13 @@ class HipContext(object):
 
     def scene_plan(self, n_images, rows_per_image, ray_idxs, feature_table, cameras, vox, rvc, Sr,
                    msgs, acc0, acc1, depth, prior, patch_rows, acc_fixed=None, order=None,
-                   depth_image=None, sweep_xcd_chunk=0):
+                   depth_image=None, sweep_xcd_chunk=0, stats=None, stats_image=None):
         """An rn_scene_plan over the caller's buffers, every tensor validated ONCE here; the
         returned object (which keeps them alive) goes to scene_run.  depth_image [n_images, R]:
-        the depth sweeps write the maps in ray-index (pixel) order there instead of `depth`."""
+        the depth sweeps write the maps in ray-index (pixel) order there instead of `depth`.
+        stats [3, rows] / stats_image [3, n_images, R]: the depth sweeps also write confidence,
+        expected depth and depth std (rn_scene_depth_stats) next to the depths -- in row order,
+        or, with depth_image, in pixel order."""
         n, rows = len(ray_idxs), int(n_images) * int(rows_per_image)
         f32, i32, ra = torch.float32, torch.int32, self._row_align
         assert rows_per_image % 256 == 0 and n <= rows_per_image
@@ -704,11 +707,22 @@ class HipContext(object):
                 lo, hi = int(ray_idxs.min()), int(ray_idxs.max())
                 assert 0 <= lo and hi < depth_image.shape[1], (lo, hi, tuple(depth_image.shape))
             pl.depth_image, pl.depth_image_stride = depth_image.data_ptr(), int(depth_image.shape[1])
+        pl.stats, pl.stats_image, pl.stats_image_stride = None, None, 0
+        if stats is not None:
+            assert tuple(stats.shape) == (3, rows), tuple(stats.shape)
+            _chk(stats, f32, 3 * rows, "stats")
+            pl.stats = stats.data_ptr()
+        if stats_image is not None:
+            assert depth_image is not None and \
+                tuple(stats_image.shape) == (3,) + tuple(depth_image.shape), tuple(stats_image.shape)
+            _chk(stats_image, f32, 3 * depth_image.numel(), "stats_image")
+            pl.stats_image = stats_image.data_ptr()
+            pl.stats_image_stride = int(depth_image.numel())
         # (the tensors the struct points into live as long as it does.  No `byref(pl)` is kept ON
         # pl: that is a reference cycle through a ctypes object the collector does not track --
         # every plan ever built, with its 7 GB of buffers, stayed allocated: round 6)
         pl._keepalive = (ray_idxs, feature_table, cameras, vox, rvc, Sr, msgs, acc0, acc1, depth,
-                         acc_fixed, order, seg, depth_image)
+                         acc_fixed, order, seg, depth_image, stats, stats_image)
         return pl
 
     def scene_run(self, plan, phases, iteration=0, image=-1):
@@ -798,3 +812,26 @@ class HipContext(object):
                                             _ptr(acc), _ptr(msgs), _ptr(center),
                                             int(rays_per_center), _ptr(S_new), _ptr(depth_map),
                                             _stream()))
+
+    def scene_depth_stats(self, Sr, vox, rvc, acc, msgs, center, S_new, depth_map, stats,
+                          rays_per_center=0, stats_offset=0):
+        """rn_scene_depth_stats: scene_depth plus stats [3, S] -- confidence, expected depth and
+        depth std of every ray's distribution, ray i at stats[:, stats_offset + i].  depth_map and
+        stats are required."""
+        n = self._chk_rows(Sr, vox, rvc, msgs, acc)
+        _chk(S_new, torch.float32, n * self.M, "S_new", optional=True)
+        _chk(depth_map, torch.float32, n, "depth_map")
+        _chk(stats, torch.float32, 3 * n, "stats")
+        stats_offset = int(stats_offset)
+        if stats.dim() != 2 or stats.shape[0] != 3 or stats_offset < 0 or \
+                stats_offset + n > stats.shape[1]:
+            raise ValueError("stats: expected shape (3, >= %d), got %s"
+                             % (stats_offset + n, tuple(stats.shape)))
+        groups = (n + rays_per_center - 1) // rays_per_center if rays_per_center > 0 else 1
+        _chk(center, torch.float32, 4 * groups if rays_per_center > 0 else 3, "center", align=4)
+        self._check(self.lib.rn_scene_depth_stats(self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc),
+                                                  _ptr(acc), _ptr(msgs), _ptr(center),
+                                                  int(rays_per_center), _ptr(S_new),
+                                                  _ptr(depth_map),
+                                                  ctypes.c_void_p(stats.data_ptr() + 4 * stats_offset),
+                                                  int(stats.shape[1]), _stream()))

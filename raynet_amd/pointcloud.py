@@ -94,28 +94,45 @@ class Pointcloud(object):
 
 
 class PointcloudFromDepthMaps(Pointcloud):
-    """raynet/pointcloud.py:76-160.  depthmaps: .npy file names (as the reference) or arrays."""
+    """raynet/pointcloud.py:76-160.  depthmaps: .npy file names (as the reference) or arrays.
+    confidences (file names or arrays like depthmaps, one per frame: the forward pass's
+    `confidence` maps) and min_confidence: pixels whose confidence is below the threshold are
+    dropped with the unwanted ones; the defaults select what the reference selects."""
 
-    def __init__(self, scene, frame_idxs, depthmaps, borders=40):
+    def __init__(self, scene, frame_idxs, depthmaps, borders=40, confidences=None,
+                 min_confidence=0.0):
         self._scene = scene
         self._frame_idxs = frame_idxs
         self._depthmaps = depthmaps
         self._borders = borders
         self._points = None
+        self._min_confidence = float(min_confidence)
+        if confidences is not None and len(confidences) != len(frame_idxs):
+            raise ValueError("%d confidence maps for %d frames" % (len(confidences), len(frame_idxs)))
+        if confidences is None and self._min_confidence > 0:
+            raise ValueError("min_confidence=%g needs the confidence maps" % self._min_confidence)
+        self._confidence_of = dict(zip(frame_idxs, confidences)) if confidences is not None else None
 
     @staticmethod
     def _load(d):
         return np.load(d) if isinstance(d, str) else np.asarray(d)
 
-    def _selected_pixels(self, G):
+    def _selected_pixels(self, G, confidence=None):
         """Indices u*H + v of the pixels that survive _remove_unwanted_points
-        (pointcloud.py:91-119), in the reference's order."""
+        (pointcloud.py:91-119), in the reference's order -- and, given the frame's confidence
+        map, whose confidence is not below min_confidence."""
         H, W = G.shape
         b = self._borders
         idxs = torch.arange(H * W, device="cuda").reshape(W, H).t()
         G = _dev(G, torch.float32)
         sl = (slice(b, H - b), slice(b, W - b))
-        return idxs[sl][G[sl] != 0]
+        keep = G[sl] != 0
+        if confidence is not None:
+            C = _dev(self._load(confidence), torch.float32)
+            if tuple(C.shape) != (H, W):
+                raise ValueError("confidence map %s for a %s depth map" % (tuple(C.shape), (H, W)))
+            keep = keep & ~(C[sl] < self._min_confidence)
+        return idxs[sl][keep]
 
     def _all_points(self, frame, depth):
         """(3, H*W) float64 device points of every pixel of `frame` (pointcloud.py:121-147)."""
@@ -133,7 +150,9 @@ class PointcloudFromDepthMaps(Pointcloud):
 
     def _generate_points_per_image(self, frame, predicted_depth):
         depth = self._load(predicted_depth)
-        sel = self._selected_pixels(self._scene.get_depth_map(frame))
+        sel = self._selected_pixels(
+            self._scene.get_depth_map(frame),
+            self._confidence_of[frame] if self._confidence_of is not None else None)
         return self._all_points(frame, depth)[:, sel]
 
     @property
@@ -149,13 +168,13 @@ class PointcloudFromDepthMapsWithConsistency(PointcloudFromDepthMaps):
     """raynet/pointcloud.py:162-246."""
 
     def __init__(self, scene, frame_idxs, depthmaps, borders=40, consistency_threshold=0.75,
-                 n_neighbors=5):
+                 n_neighbors=5, confidences=None, min_confidence=0.0):
         self._consistency_threshold = consistency_threshold
         self._n_neighbors = n_neighbors
         self._camera_neighbors = None
         self._frame_idxs_map = dict(zip(frame_idxs, range(len(frame_idxs))))
-        super(PointcloudFromDepthMapsWithConsistency, self).__init__(scene, frame_idxs, depthmaps,
-                                                                     borders)
+        super(PointcloudFromDepthMapsWithConsistency, self).__init__(
+            scene, frame_idxs, depthmaps, borders, confidences, min_confidence)
 
     def _neighbor_frames(self, frame):
         if self._camera_neighbors is None:
@@ -181,9 +200,11 @@ class PointcloudFromDepthMapsWithConsistency(PointcloudFromDepthMaps):
 
 
 def get_pointcloud(scene, frame_idxs, depthmaps, with_consistency, **kwargs):
-    """raynet/pointcloud.py:248-269."""
+    """raynet/pointcloud.py:248-269; optional kwargs confidences, min_confidence."""
+    conf = dict(confidences=kwargs.get("confidences"),
+                min_confidence=kwargs.get("min_confidence", 0.0))
     if with_consistency:
         return PointcloudFromDepthMapsWithConsistency(
             scene, frame_idxs, depthmaps, kwargs["borders"], kwargs["consistency_threshold"],
-            kwargs["n_neighbors"])
-    return PointcloudFromDepthMaps(scene, frame_idxs, depthmaps, kwargs["borders"])
+            kwargs["n_neighbors"], **conf)
+    return PointcloudFromDepthMaps(scene, frame_idxs, depthmaps, kwargs["borders"], **conf)

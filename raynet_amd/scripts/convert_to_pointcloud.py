@@ -9,7 +9,9 @@ it as OUTPUT_DIR/predicted_pc_s_%d.ply.  With filters -- the scene's observation
 (VoxelMask; DTU scans have one) and --min_distance d (ReduceDensity: no two kept points within
 d; -1, the default, is off) -- the filtered cloud is saved as filtered_predicted_pc_s_%d.ply
 as well, and each filter leaves its own PLY in OUTPUT_DIR.  The flags are the reference's, with
-its defaults; --seed is new: the thinning's visiting order (the reference shuffles unseeded).
+its defaults; --seed is new: the thinning's visiting order (the reference shuffles unseeded),
+and so is --min_confidence X: pixels whose confidence (PREDICTIONS_DIR/confidence_%03d.npy, what
+`forward_pass --depth_statistics` writes) is below X do not become points.
 """
 import argparse
 import os
@@ -69,6 +71,9 @@ def build_parser():
     p.add_argument("--with_consistency_check", action="store_true")
     p.add_argument("--seed", default=0, type=int,
                    help="--min_distance: the seed of the thinning's visiting order")
+    p.add_argument("--min_confidence", default=None, type=float,
+                   help="Drop the pixels whose confidence (confidence_%%03d.npy in the predictions "
+                        "directory, from forward_pass --depth_statistics) is below this (default: off)")
     return p
 
 
@@ -97,9 +102,20 @@ def run(scene, args):
                                           output_directory=args.output_directory, seed=args.seed)
     fmt = find_format(args.predictions_directory, args.pred_suffix, frame_idxs[0])
     depthmaps = [os.path.join(args.predictions_directory, fmt % (i,)) for i in frame_idxs]
+    confidence = {}
+    if getattr(args, "min_confidence", None) is not None:
+        cfmt = find_format(args.predictions_directory, "confidence", frame_idxs[0])
+        files = [os.path.join(args.predictions_directory, cfmt % (i,)) for i in frame_idxs]
+        missing = [f for f in files if not os.path.isfile(f)]
+        if missing:
+            raise SystemExit(
+                "--min_confidence: %d of %d confidence maps are missing (first: %s); write them "
+                "with `forward_pass --depth_statistics`" % (len(missing), len(files), missing[0]))
+        confidence = dict(confidences=files, min_confidence=args.min_confidence)
     predicted_pointcloud = get_pointcloud(
         scene, frame_idxs, depthmaps, args.with_consistency_check, borders=args.borders,
-        consistency_threshold=args.consistency_threshold, n_neighbors=args.n_neighbors)
+        consistency_threshold=args.consistency_threshold, n_neighbors=args.n_neighbors,
+        **confidence)
     print("Saving predicted point-cloud for scene %d ..." % (args.scene_idx,))
     predicted_pointcloud.save_ply(
         os.path.join(args.output_directory, "predicted_pc_s_%d.ply" % (args.scene_idx,)))
