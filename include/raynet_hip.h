@@ -680,6 +680,46 @@ int rn_cloud_zbuffer_counted(rn_ctx *ctx, int32_t n_points, const float *points,
                              const double *cameras, int32_t H, int32_t W, uint32_t *zbuf,
                              uint64_t *counts, void *stream);
 
+/* ---- training batches: rays of many reference views in one launch ---- */
+
+/* n candidate rays of ONE scene, each with its own reference view.  All device memory.
+ *   view [n] i32, ray_idxs [n] i32 (pixel u * H + v), depth [n] f32 (ground-truth distance to the
+ *   camera centre), cams [n_views][28] f32 (P_pinv [4][3] | centre [4] | P [3][4], row-major),
+ *   nbr [n_views][N] i32 (the views a ray of view v is projected into, nbr[v][0] == v by
+ *   convention); H, W, D and the bounding box are the context's.
+ * Outputs, every fp32 operation rounded on its own, in this order:
+ *   points [n][D][4]      what rn_sample_points gives with cams[view] (bit for bit);
+ *   target [n][4]         ray_i = (Pinv_i0 u + Pinv_i1 v) + Pinv_i2, i = 0..3;  a = ray / ray_3 -
+ *                         centre;  norm = sqrt((a0^2 + a1^2) + a2^2);  target = a / norm * depth +
+ *                         centre, w = 1 (depth taken as 0 for a ray without depth);
+ *   centres [n][N][D][2]  i32 (x = column, y = row): q = ((P0 X + P1 Y) + P2 Z) + P3 per row of
+ *                         cams[nbr[view][j]].P, x = qx / qz, y = qy / qz, rounded half to even and
+ *                         converted (NaN -> 0, beyond int32 -> the nearest end);
+ *   flags [n] i32         1 no depth (depth == 0 or not finite) | 2 target not inside the box
+ *                         (some coordinate < min, > max or NaN) | 4 the ray misses the box
+ *                         (t_near > t_far of the slab test, before its swap) | 8 some patch of
+ *                         some view crosses an image border: not (cx - w/2 >= 0, cy - h/2 >= 0,
+ *                         cx + w/2 + w%2 <= W, cy + h/2 + h%2 <= H), or x, y not finite, or
+ *                         qz <= 0.  A ray is valid iff its flags are 0.
+ * A view outside [0, n_views), a ray index outside [0, H W) or such a neighbour is never read
+ * through: the kernel tests them, writes zeros and flags = 16 for that ray and the CALL returns
+ * RN_ERR_INVALID -- decided on the host from one word the kernel ORs into, so the entry
+ * synchronises `stream`.  n == 0: RN_OK, no launch.  n * N * D < 2^30. */
+int rn_batch_rays(rn_ctx *ctx, int32_t n, const int32_t *view, const int32_t *ray_idxs,
+                  const float *depth, const float *cams, int32_t n_views, const int32_t *nbr,
+                  int32_t N, int32_t patch_h, int32_t patch_w, float *points, float *target,
+                  int32_t *centres, int32_t *flags, void *stream);
+
+/* The patches around rn_batch_rays' centres.  images [n_views][H][W][C] f32 (channels-last),
+ * view [n], centres [n][N][D][2], nbr [n_views][N] as above.  patches [N][n][D][patch_h][patch_w][C]
+ * f32: patch j of ray r and sample k holds image nbr[view[r]][j] at rows cy - h/2 .. cy + h/2 +
+ * h%2 - 1 and columns cx - w/2 .. cx + w/2 + w%2 - 1, zero wherever that lies outside the image.
+ * EVERY texel read is tested against the image: a centre may be any int32.  Index checks, the
+ * synchronisation and n == 0 as for rn_batch_rays. */
+int rn_batch_patches(rn_ctx *ctx, int32_t n, const float *images, int32_t n_views, int32_t C,
+                     const int32_t *view, const int32_t *centres, const int32_t *nbr, int32_t N,
+                     int32_t patch_h, int32_t patch_w, float *patches, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -41,7 +41,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_prepare.inl"), os.path.join(CSRC, "raynet_mrf.inl"),
             os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"),
             os.path.join(CSRC, "raynet_mesh.inl"), os.path.join(CSRC, "raynet_filters.inl"),
-            os.path.join(CSRC, "raynet_cloud.inl"), HEADER]
+            os.path.join(CSRC, "raynet_cloud.inl"), os.path.join(CSRC, "raynet_batch.inl"), HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
         # RAYNET_HIP_LIB names ANOTHER build of the library (a variant somebody made on purpose):
@@ -185,6 +185,8 @@ SIGNATURES = {
     "rn_thin_round": [_P, _I, _P, _I, _P, _P, _P, _P, _D, _P, _P, _P],
     "rn_cloud_zbuffer": [_P, _I, _P, _I, _P, _I, _I, _P, _P],
     "rn_cloud_zbuffer_counted": [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P],
+    "rn_batch_rays": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "rn_batch_patches": [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

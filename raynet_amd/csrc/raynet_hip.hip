@@ -332,6 +332,8 @@ void rn_destroy(rn_ctx *ctx) {
     if (ctx->box_stats) hipFree(ctx->box_stats);
     if (ctx->scalar_dev) hipFree(ctx->scalar_dev);
     if (ctx->box_stats_host) hipHostFree(ctx->box_stats_host);
+    if (ctx->batch_bad) hipFree(ctx->batch_bad);
+    if (ctx->batch_bad_host) hipHostFree(ctx->batch_bad_host);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
@@ -1166,3 +1168,6 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 
 // ground-truth depth of a point cloud: every view's z-buffer in one pass
 #include "raynet_cloud.inl"
+
+// training batches of rays from many reference views
+#include "raynet_batch.inl"

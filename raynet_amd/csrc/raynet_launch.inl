@@ -17,6 +17,9 @@ struct rn_ctx {
     float first_prior = 0.0f, first_occ = 0.0f;
     bool have_first_occ = false;
     float *scalar_dev = nullptr;      // 4 bytes of device scratch owned by the context
+    // rn_batch_rays / rn_batch_patches: "an index was out of range" (device word, pinned mirror),
+    // allocated by the first such call
+    int32_t *batch_bad = nullptr, *batch_bad_host = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // slab boxes (rn_scene_bind_slab_boxes): table, the list buffer it describes, and the row
     // range rn_scene_prepare_all last filled

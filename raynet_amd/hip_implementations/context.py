@@ -421,6 +421,65 @@ class HipContext(object):
                                                           _ptr(cameras), H, W, _ptr(zbuf),
                                                           _ptr(counts), _stream()))
 
+    # ---- training batches of rays from many reference views (train_network/ray_sampler.py) ---
+    BATCH_CAMERA_FLOATS = 28      # P_pinv [4][3] | centre [4] | P [3][4]
+
+    def _chk_batch_tables(self, view, nbr, n):
+        _chk(view, torch.int32, n, "view")
+        if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= 16:
+            raise ValueError("nbr: expected shape (V, N) with 1 <= N <= 16, got %s" % (tuple(nbr.shape),))
+        V, N = int(nbr.shape[0]), int(nbr.shape[1])
+        _chk(nbr, torch.int32, V * N, "nbr")
+        return V, N
+
+    def batch_rays(self, view, ray_idxs, depth, cams, nbr, patch_shape, points, target, centres,
+                   flags):
+        """rn_batch_rays: n candidate rays, each of its own reference view, in one launch.
+        view, ray_idxs [n] i32, depth [n] f32, cams (V, 28) f32, nbr (V, N) i32 -> points
+        [n, D, 4], target [n, 4], centres [n, N, D, 2] i32, flags [n] i32 (0 = valid).  An index
+        out of range raises (the entry decides it from the kernel's own tests and synchronises)."""
+        n = len(ray_idxs)
+        V, N = self._chk_batch_tables(view, nbr, n)
+        h, w = int(patch_shape[0]), int(patch_shape[1])
+        if h < 1 or w < 1:
+            raise ValueError("patch_shape: at least 1 x 1, got %s" % (tuple(patch_shape),))
+        if n * N * self.D >= 1 << 30:
+            raise ValueError("n * N * D = %d: at most 2^30 per call" % (n * N * self.D))
+        _chk(ray_idxs, torch.int32, n, "ray_idxs")
+        _chk(depth, torch.float32, n, "depth")
+        _chk(cams, torch.float32, V * self.BATCH_CAMERA_FLOATS, "cams")
+        if tuple(cams.shape) != (V, self.BATCH_CAMERA_FLOATS):
+            raise ValueError("cams: expected shape (%d, 28), got %s" % (V, tuple(cams.shape)))
+        _chk(points, torch.float32, n * self.D * 4, "points", align=16)
+        _chk(target, torch.float32, n * 4, "target", align=16)
+        _chk(centres, torch.int32, n * N * self.D * 2, "centres", align=8)
+        _chk(flags, torch.int32, n, "flags")
+        self._check(self.lib.rn_batch_rays(self._h, n, _ptr(view), _ptr(ray_idxs), _ptr(depth),
+                                           _ptr(cams), V, _ptr(nbr), N, h, w, _ptr(points),
+                                           _ptr(target), _ptr(centres), _ptr(flags), _stream()))
+
+    def batch_patches(self, images, view, centres, nbr, patch_shape, patches):
+        """rn_batch_patches: images (V, H, W, C) f32, view [n], centres [n, N, D, 2], nbr (V, N)
+        -> patches (N, n, D, h, w, C) f32, zero outside the images."""
+        n = len(view)
+        V, N = self._chk_batch_tables(view, nbr, n)
+        h, w = int(patch_shape[0]), int(patch_shape[1])
+        if h < 1 or w < 1:
+            raise ValueError("patch_shape: at least 1 x 1, got %s" % (tuple(patch_shape),))
+        if images.dim() != 4 or tuple(images.shape[:3]) != (V, self.H, self.W):
+            raise ValueError("images: expected shape (%d, %d, %d, C), got %s"
+                             % (V, self.H, self.W, tuple(images.shape)))
+        C = int(images.shape[3])
+        if self.D * h * w * C >= 1 << 30 or self.H * self.W * C >= 1 << 31:
+            raise ValueError("patches of %d x %d x %d x %d floats per ray and view: too large"
+                             % (self.D, h, w, C))
+        _chk(images, torch.float32, V * self.H * self.W * C, "images")
+        _chk(centres, torch.int32, n * N * self.D * 2, "centres", align=8)
+        _chk(patches, torch.float32, N * n * self.D * h * w * C, "patches")
+        self._check(self.lib.rn_batch_patches(self._h, n, _ptr(images), V, C, _ptr(view),
+                                              _ptr(centres), _ptr(nbr), N, h, w, _ptr(patches),
+                                              _stream()))
+
     KERNEL_NAMES = {1: "traverse", 2: "sweep_map", 3: "bp", 4: "depth", 5: "acc", 6: "other", 7: "scatter"}
 
     # ---- ground truth from scene meshes (raynet_amd/mesh.py) ----------------------------
