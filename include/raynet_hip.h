@@ -720,6 +720,94 @@ int rn_batch_patches(rn_ctx *ctx, int32_t n, const float *images, int32_t n_view
                      const int32_t *view, const int32_t *centres, const int32_t *nbr, int32_t N,
                      int32_t patch_h, int32_t patch_w, float *patches, void *stream);
 
+/* ---- sampling schemes: WHERE on the viewing ray the D samples lie ----
+ *
+ * The ray of a pixel is what sample_in_bbox computes (sampling_schemes.cu:44-90): pixel (u, v) =
+ * (ray_idx / H, ray_idx % H); o_r = fl32(Pinv_r0 u) + fl32(Pinv_r1 v) + Pinv_r2 summed in fp64,
+ * r = 0..3; dir_i = fl32(o_i / o_3 - centre_i).  The schemes share it.
+ *
+ * RN_SAMPLE_IN_BBOX       the box segment of the slab test, sample k = plane_point(s, e, k, D) =
+ *                         s + k (e - s) / (D - 1) per coordinate in fp32: the old entries.
+ * RN_SAMPLE_IN_RANGE      (raynet/common/sampling_schemes.py:178-237) range = (r0, r1):
+ *                         d^ = dir / sqrt((dir0^2 + dir1^2) + dir2^2), s = centre + r0 d^,
+ *                         e = centre + r1 d^, sample k = plane_point(s, e, k, D); every fp32
+ *                         operation rounded on its own, in this order.  The box plays no part.
+ * RN_SAMPLE_IN_DISPARITY  (sampling_schemes.py:240-297) the box segment (p_near, p_far) is
+ *                         projected into the far view -- the LAST view of the ray's neighbour
+ *                         list --, D pixels lie evenly between the two projections, each is
+ *                         back-projected through the far view's P_inv, and sample k is the point
+ *                         ON THE VIEWING RAY closest to that ray (utils/geometry.py:243-312, first
+ *                         returned point).  In fp64 from the fp32 segment ends on, one rounding
+ *                         to fp32 at the end; with a.b = (a0 b0 + a1 b1) + a2 b2:
+ *                           q = ((P0 X + P1 Y) + P2 Z) + P3 per row of far_P;
+ *                           pix = (rint(qx/qz), rint(qy/qz)), half to even (Image.project rounds)
+ *                           t_k = fl32(k * (1 / (D - 1))) (fp64 product), t_{D-1} = 1
+ *                           pu = fl32(u_near + t_k (u_far - u_near)), pv likewise (Image.ray
+ *                           takes a float32 pixel)
+ *                           o_r = (Pinv_r0 pu + Pinv_r1 pv) + Pinv_r2;  a2 = o / o_3 - c2
+ *                           a1 = dir, c1 = centre, c2 = far_centre
+ *                           div = (a1.a1)(a2.a2) - (a1.a2)(a1.a2)
+ *                           t1 = (-(a2.a2) (a1.c1 - a1.c2) + (a1.a2) (a2.c1 - a2.c2)) / div
+ *                           point = fl32(c1 + a1 t1)
+ *                         A ray that misses the box (t_near > t_far; the reference returns None)
+ *                         has no samples: its D points are the camera centre with w = 0, its
+ *                         K9 column the sweep of that one point (1 / D each), its K10 depth 0.
+ *                         Every other point has w = 1.
+ * The POD is host memory, read during the call.  The far view is used by RN_SAMPLE_IN_DISPARITY
+ * only, the range by RN_SAMPLE_IN_RANGE only. */
+typedef enum {
+    RN_SAMPLE_IN_BBOX = 0,
+    RN_SAMPLE_IN_RANGE = 1,
+    RN_SAMPLE_IN_DISPARITY = 2
+} rn_sampling_scheme;
+
+typedef struct {
+    int32_t scheme;          /* rn_sampling_scheme */
+    float range[2];          /* r0 < r1, both finite and > 0 */
+    float far_P[12];         /* [3][4] row-major */
+    float far_P_inv[12];     /* [4][3] row-major */
+    float far_centre[4];
+} rn_sampling;
+
+/* Every entry below: `sampling` NULL, an unknown scheme, a range that is not 0 < r0 < r1 <
+ * infinity (RN_SAMPLE_IN_RANGE) or D < 2 is RN_ERR_INVALID with a message in rn_last_error and
+ * no launch (D < 2 is refused by rn_create already, which has no context to leave a message in:
+ * the entries' own check guards a context made some other way); n == 0 is RN_OK without a launch; RN_SAMPLE_IN_BBOX runs the old entry's kernel
+ * (same bits).  RN_SAMPLE_IN_RANGE sweeps run the old entries' kernels on the range segments
+ * (the context keeps ONE buffer of segments: per context, issue them on one stream at a time);
+ * RN_SAMPLE_IN_DISPARITY sweeps take one ray per wavefront, also where D <= 32 packs two or four
+ * bbox rays into one. */
+
+/* K8 under a scheme (sampling_schemes.py:183-195, :241-297; sample_points.py:12-54):
+ * points [n][D][4] */
+int rn_sample_points_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *P_inv,
+                            const float *camera_center, const rn_sampling *sampling,
+                            float *points, void *stream);
+
+/* K9 under a scheme (similarities.py:101-130 with scripts/forward_pass.py:91's scheme): S [n][D] */
+int rn_mvcnn_similarities_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs,
+                                 const float *features, const float *P, const float *P_inv,
+                                 const float *camera_center, const rn_sampling *sampling,
+                                 float *S, void *stream);
+
+/* K10 under a scheme (similarities.py:252-285): points are rn_sample_points_scheme's bit for
+ * bit, the plane is the first maximum of the column, depth_map its point's distance to the
+ * camera centre */
+int rn_mvcnn_depth_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *features,
+                          const float *P, const float *P_inv, const float *camera_center,
+                          const rn_sampling *sampling, float *S, float *points,
+                          float *depth_map, void *stream);
+
+/* rn_batch_rays under a scheme (pretrain_network.py:191's sample generators): points are what
+ * rn_sample_points_scheme gives with cams[view] and, for RN_SAMPLE_IN_DISPARITY, the far view
+ * cams[nbr[view][N - 1]] (the POD's far view is not read); target, centres and flags follow
+ * rn_batch_rays' definitions on those points.  Flag 4 is never set by RN_SAMPLE_IN_RANGE. */
+int rn_batch_rays_scheme(rn_ctx *ctx, int32_t n, const int32_t *view, const int32_t *ray_idxs,
+                         const float *depth, const float *cams, int32_t n_views,
+                         const int32_t *nbr, int32_t N, int32_t patch_h, int32_t patch_w,
+                         const rn_sampling *sampling, float *points, float *target,
+                         int32_t *centres, int32_t *flags, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -104,6 +104,15 @@ class ScenePlan(ctypes.Structure):
     ]
 
 
+class Sampling(ctypes.Structure):
+    # rn_sampling (include/raynet_hip.h)
+    _fields_ = [("scheme", ctypes.c_int32), ("range", ctypes.c_float * 2),
+                ("far_P", ctypes.c_float * 12), ("far_P_inv", ctypes.c_float * 12),
+                ("far_centre", ctypes.c_float * 4)]
+
+
+SAMPLING_SCHEMES = {"sample_in_bbox": 0, "sample_in_range": 1, "sample_in_disparity": 2}
+
 RN_RUN_PREPARE, RN_RUN_SWEEP, RN_RUN_COMBINE, RN_RUN_DEPTH, RN_RUN_DEPTH_RANGE = 1, 2, 4, 8, 16
 
 _P = ctypes.c_void_p
@@ -187,6 +196,11 @@ SIGNATURES = {
     "rn_cloud_zbuffer_counted": [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     "rn_batch_rays": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "rn_batch_patches": [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
+    "rn_sample_points_scheme": [_P, _I, _P, _P, _P, ctypes.POINTER(Sampling), _P, _P],
+    "rn_mvcnn_similarities_scheme": [_P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(Sampling), _P, _P],
+    "rn_mvcnn_depth_scheme": [_P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(Sampling), _P, _P, _P, _P],
+    "rn_batch_rays_scheme": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, ctypes.POINTER(Sampling),
+                             _P, _P, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

@@ -16,6 +16,7 @@
 namespace {
 
 constexpr int BATCH_CAMERA_FLOATS = 28;     // P_pinv [4][3] | centre [4] | P [3][4], row-major
+static_assert(BATCH_CAMERA_FLOATS == CAMERA_FLOATS, "the schemes read a far view out of the table");
 constexpr int BATCH_FLAG_NO_DEPTH = 1, BATCH_FLAG_TARGET_OUTSIDE = 2, BATCH_FLAG_MISSES_BOX = 4,
               BATCH_FLAG_BORDER = 8;
 
@@ -150,6 +151,98 @@ __global__ __launch_bounds__(BLOCK) void k_batch_rays(
     }
 }
 
+// k_batch_rays with the D sample points where sample_in_range / sample_in_disparity put them
+// (SCHEME_RANGE / SCHEME_DISPARITY); target, centres and flags as above on
+// those points.  sample_in_disparity's far view is the last of the ray's own neighbour list,
+// nbr[view][N - 1]; a ray of it that misses the box gets the camera centre with w = 0 D times and
+// BATCH_FLAG_MISSES_BOX.  sample_in_range never sets that flag: the box plays no part in it.
+// A second kernel, not a flag in the first: k_batch_rays keeps its instructions
+// (profiles/sampling_schemes_isa_identity.txt).
+template <int SCHEME>
+__global__ __launch_bounds__(BLOCK) void k_batch_rays_scheme(
+    Params p, int n, const int32_t *__restrict__ view, const int32_t *__restrict__ ray_idxs,
+    const float *__restrict__ depth, const float *__restrict__ cams, int V,
+    const int32_t *__restrict__ nbr, int N, int ph, int pw, float *points, float *target,
+    int32_t *centres, int32_t *flags, int32_t *bad, float r0, float r1) {
+    int lane;
+    const int r = ray_of_wave(n, lane);
+    if (r < 0) return;
+    const int vw = uniform(view[r]), ri = uniform(ray_idxs[r]);
+    float4 *row = reinterpret_cast<float4 *>(points) + (size_t)r * p.D;
+    int2 *crow = reinterpret_cast<int2 *>(centres) + (size_t)r * N * p.D;
+    bool ok = vw >= 0 && vw < V && ri >= 0 && ri < p.H * p.W;
+    if (ok)
+        for (int j = 0; j < N; j++) {
+            const int nv = uniform(nbr[(size_t)vw * N + j]);
+            ok = ok && nv >= 0 && nv < V;
+        }
+    if (!ok) {
+        // an index that names no camera / pixel: nothing is read through it; the call fails
+        for (int k = lane; k < p.D; k += WAVE) row[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int k = lane; k < N * p.D; k += WAVE) crow[k] = make_int2(0, 0);
+        if (lane == 0) {
+            reinterpret_cast<float4 *>(target)[r] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            flags[r] = 16;
+            atomicOr(bad, 1);
+        }
+        return;
+    }
+    const float *cam = cams + (size_t)vw * BATCH_CAMERA_FLOATS, *cc = cam + 12;
+
+    // ---- ground-truth point (every lane the same values; lane 0 stores)
+    const float u = (float)(ri / p.H), v = (float)(ri % p.H);
+    float ray[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) ray[i] = (cam[3 * i] * u + cam[3 * i + 1] * v) + cam[3 * i + 2];
+    float a[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) a[i] = ray[i] / ray[3] - cc[i];
+    const float norm = sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+    const float dr = depth[r];
+    const bool no_depth = dr == 0.0f || !(fabsf(dr) < INFINITY);
+    const float d = no_depth ? 0.0f : dr;
+    float t[3];
+    bool outside = false;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        t[i] = a[i] / norm * d + cc[i];
+        outside = outside || !(t[i] >= p.bbox[i] && t[i] <= p.bbox[3 + i]);
+    }
+
+    // ---- sample points and their patch centres in the ray's N views
+    SchemeRay sr;
+    const float *far = cams + (size_t)uniform(nbr[(size_t)vw * N + N - 1]) * BATCH_CAMERA_FLOATS;
+    scheme_ray<SCHEME == SCHEME_DISPARITY>(p, SCHEME, r0, r1, ri, cam, cc, far, sr);
+    const bool misses = sr.missed;
+    const int lo_x = pw / 2, lo_y = ph / 2, hi_x = p.W - pw / 2 - pw % 2, hi_y = p.H - ph / 2 - ph % 2;
+    unsigned long long crossing = 0;
+    for (int base = 0; base < p.D; base += WAVE) {
+        const int k = base + lane;
+        const bool live = k < p.D;
+        float pt[3];
+        scheme_point<SCHEME == SCHEME_DISPARITY>(sr, live ? k : p.D - 1, p.D, pt);
+        if (live) row[k] = make_float4(pt[0], pt[1], pt[2], misses ? 0.0f : 1.0f);
+        for (int j = 0; j < N; j++) {
+            const float *P = cams + (size_t)uniform(nbr[(size_t)vw * N + j]) * BATCH_CAMERA_FLOATS + 16;
+            const float qx = ((P[0] * pt[0] + P[1] * pt[1]) + P[2] * pt[2]) + P[3];
+            const float qy = ((P[4] * pt[0] + P[5] * pt[1]) + P[6] * pt[2]) + P[7];
+            const float qz = ((P[8] * pt[0] + P[9] * pt[1]) + P[10] * pt[2]) + P[11];
+            const float x = qx / qz, y = qy / qz;
+            const int cx = batch_to_i32(__builtin_rintf(x)), cy = batch_to_i32(__builtin_rintf(y));
+            // patches_inside's four inequalities with the sums moved across (no overflow)
+            const bool inside = fabsf(x) < INFINITY && fabsf(y) < INFINITY && qz > 0.0f &&
+                                cx >= lo_x && cy >= lo_y && cx <= hi_x && cy <= hi_y;
+            crossing |= __builtin_amdgcn_ballot_w64(live && !inside);
+            if (live) crow[(size_t)j * p.D + k] = make_int2(cx, cy);
+        }
+    }
+    if (lane == 0) {
+        reinterpret_cast<float4 *>(target)[r] = make_float4(t[0], t[1], t[2], 1.0f);
+        flags[r] = (no_depth ? BATCH_FLAG_NO_DEPTH : 0) | (outside ? BATCH_FLAG_TARGET_OUTSIDE : 0) |
+                   (misses ? BATCH_FLAG_MISSES_BOX : 0) | (crossing ? BATCH_FLAG_BORDER : 0);
+    }
+}
+
 // grid = (n, N): workgroup (r, j) writes out[j][r][D][ph][pw][C] -- channels-last like the
 // images, so a patch row is pw * C consecutive floats on both sides.
 __global__ __launch_bounds__(BLOCK) void k_batch_patches(
@@ -216,6 +309,33 @@ int rn_batch_rays(rn_ctx *ctx, int32_t n, const int32_t *view, const int32_t *ra
                        target, centres, flags, ctx->batch_bad);
     RN_LAUNCH_CHECK(ctx);
     return batch_indices_ok(ctx, S(stream), "rn_batch_rays");
+}
+
+int rn_batch_rays_scheme(rn_ctx *ctx, int32_t n, const int32_t *view, const int32_t *ray_idxs,
+                         const float *depth, const float *cams, int32_t n_views,
+                         const int32_t *nbr, int32_t N, int32_t patch_h, int32_t patch_w,
+                         const rn_sampling *sampling, float *points, float *target,
+                         int32_t *centres, int32_t *flags, void *stream) {
+    if (!ctx) return RN_ERR_INVALID;
+    SchemeArgs sa;
+    if (int rc = scheme_args(ctx, sampling, "rn_batch_rays_scheme", sa)) return rc;
+    if (sa.id == SCHEME_BBOX)
+        return rn_batch_rays(ctx, n, view, ray_idxs, depth, cams, n_views, nbr, N, patch_h, patch_w,
+                             points, target, centres, flags, stream);
+    RN_OPEN(ctx, n, all_set(view, ray_idxs, depth, cams, nbr, points, target, centres, flags) &&
+                        n_views >= 1 && N >= 1 && N <= MAX_VIEWS && patch_h >= 1 && patch_w >= 1 &&
+                        (int64_t)n * N * ctx->p.D < ((int64_t)1 << 30));
+    int rc = batch_status_word(ctx, S(stream));
+    if (rc) return rc;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(ray_blocks(n)), dim3(BLOCK), 0, S(stream), ctx->p, n, view,
+                           ray_idxs, depth, cams, n_views, nbr, N, patch_h, patch_w, points, target,
+                           centres, flags, ctx->batch_bad, sa.r0, sa.r1);
+    };
+    if (sa.id == SCHEME_DISPARITY) go(k_batch_rays_scheme<SCHEME_DISPARITY>);
+    else go(k_batch_rays_scheme<SCHEME_RANGE>);
+    RN_LAUNCH_CHECK(ctx);
+    return batch_indices_ok(ctx, S(stream), "rn_batch_rays_scheme");
 }
 
 int rn_batch_patches(rn_ctx *ctx, int32_t n, const float *images, int32_t n_views, int32_t C,

@@ -333,6 +333,7 @@ void rn_destroy(rn_ctx *ctx) {
     if (ctx->scalar_dev) hipFree(ctx->scalar_dev);
     if (ctx->box_stats_host) hipHostFree(ctx->box_stats_host);
     if (ctx->batch_bad) hipFree(ctx->batch_bad);
+    if (ctx->range_seg) hipFree(ctx->range_seg);
     if (ctx->batch_bad_host) hipHostFree(ctx->batch_bad_host);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -490,6 +491,64 @@ int rn_mvcnn_depth(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float 
     SweepArgs a{n, ray_idxs, stacked_views(ctx->p, features), P, P_inv, camera_center, nullptr,
                 nullptr, nullptr, nullptr, nullptr, Sp, nullptr, depth_map, points};
     launch_sweep<0, false>(ctx, a, true, S(stream));
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+// ---- the same three under a sampling scheme (sampling_schemes.py:178-297)
+static_assert(RN_SAMPLE_IN_BBOX == SCHEME_BBOX && RN_SAMPLE_IN_RANGE == SCHEME_RANGE &&
+              RN_SAMPLE_IN_DISPARITY == SCHEME_DISPARITY, "the header's ids are the kernels'");
+
+int rn_sample_points_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *P_inv,
+                            const float *camera_center, const rn_sampling *sampling,
+                            float *points, void *stream) {
+    if (!ctx) return RN_ERR_INVALID;
+    SchemeArgs sa;
+    if (int rc = scheme_args(ctx, sampling, "rn_sample_points_scheme", sa)) return rc;
+    if (sa.id == SCHEME_BBOX)
+        return rn_sample_points(ctx, n, ray_idxs, P_inv, camera_center, points, stream);
+    RN_OPEN(ctx, n, all_set(ray_idxs, P_inv, camera_center, points));
+    if (sa.id == SCHEME_DISPARITY)
+        hipLaunchKernelGGL(k_sample_points_scheme<true>, dim3(ray_blocks(n)), dim3(BLOCK), 0,
+                           S(stream), ctx->p, n, ray_idxs, P_inv, camera_center, sa, points);
+    else
+        hipLaunchKernelGGL(k_sample_points_scheme<false>, dim3(ray_blocks(n)), dim3(BLOCK), 0,
+                           S(stream), ctx->p, n, ray_idxs, P_inv, camera_center, sa, points);
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mvcnn_similarities_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs,
+                                 const float *features, const float *P, const float *P_inv,
+                                 const float *camera_center, const rn_sampling *sampling,
+                                 float *Sp, void *stream) {
+    if (!ctx) return RN_ERR_INVALID;
+    SchemeArgs sa;
+    if (int rc = scheme_args(ctx, sampling, "rn_mvcnn_similarities_scheme", sa)) return rc;
+    if (sa.id == SCHEME_BBOX)
+        return rn_mvcnn_similarities(ctx, n, ray_idxs, features, P, P_inv, camera_center, Sp, stream);
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, Sp));
+    if (int rc = launch_sweep_scheme(ctx, n, ray_idxs, features, P, P_inv, camera_center, sa, Sp,
+                                     nullptr, nullptr, S(stream)))
+        return rc;
+    RN_LAUNCH_CHECK(ctx);
+    return RN_OK;
+}
+
+int rn_mvcnn_depth_scheme(rn_ctx *ctx, int32_t n, const int32_t *ray_idxs, const float *features,
+                          const float *P, const float *P_inv, const float *camera_center,
+                          const rn_sampling *sampling, float *Sp, float *points,
+                          float *depth_map, void *stream) {
+    if (!ctx) return RN_ERR_INVALID;
+    SchemeArgs sa;
+    if (int rc = scheme_args(ctx, sampling, "rn_mvcnn_depth_scheme", sa)) return rc;
+    if (sa.id == SCHEME_BBOX)
+        return rn_mvcnn_depth(ctx, n, ray_idxs, features, P, P_inv, camera_center, Sp, points,
+                              depth_map, stream);
+    RN_OPEN(ctx, n, all_set(ray_idxs, features, P, P_inv, camera_center, Sp, points, depth_map));
+    if (int rc = launch_sweep_scheme(ctx, n, ray_idxs, features, P, P_inv, camera_center, sa, Sp,
+                                     depth_map, points, S(stream)))
+        return rc;
     RN_LAUNCH_CHECK(ctx);
     return RN_OK;
 }

@@ -177,10 +177,11 @@ __device__ __forceinline__ float round_quotient_fast(float x, float rcp_n, bool 
 
 // ------------------------------------------------------------------- a1
 // sampling_schemes.cu:44-90; arithmetic identical to oracle rno_sample_in_bbox
-__device__ __forceinline__ void sample_in_bbox(const Params &p, int ray_idx,
-                                               const float *__restrict__ P_inv,
-                                               const float *__restrict__ cc, float s[3],
-                                               float e[3]) {
+// The ray of a pixel (include/raynet_hip.h, "The ray of a pixel"): fp64 back-projection with
+// P_inv, divided by the fourth coordinate, dir = ray - centre rounded to fp32 once.
+__device__ __forceinline__ void pixel_ray(const Params &p, int ray_idx,
+                                          const float *__restrict__ P_inv,
+                                          const float *__restrict__ cc, float dir[3]) {
     const float px = (float)(ray_idx / p.H);
     const float py = (float)(ray_idx % p.H);
     double o[4];
@@ -192,9 +193,14 @@ __device__ __forceinline__ void sample_in_bbox(const Params &p, int ray_idx,
         a += (double)P_inv[3 * r + 2] * 1.0;
         o[r] = a;
     }
-    float dir[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) dir[i] = (float)(o[i] / o[3] - (double)cc[i]);
+}
+// the slab test on that ray and the box segment it yields; `misses` = t_near > t_far on the
+// values the swap below then reorders
+__device__ __forceinline__ void bbox_segment(const Params &p, const float *__restrict__ cc,
+                                             const float dir[3], float s[3], float e[3],
+                                             bool &misses) {
     float t_near = -INFINITY, t_far = INFINITY;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -203,6 +209,7 @@ __device__ __forceinline__ void sample_in_bbox(const Params &p, int ray_idx,
         t_near = fmaxf(fminf(t1, t2), t_near);
         t_far = fminf(fmaxf(t1, t2), t_far);
     }
+    misses = t_near > t_far;
     const float near_mask = (fabsf(t_near) < fabsf(t_far)) ? 1.0f : 0.0f;
     const float tn = t_near * near_mask + t_far * (1 - near_mask);
     const float tf = (1 - near_mask) * t_near + near_mask * t_far;
@@ -211,6 +218,15 @@ __device__ __forceinline__ void sample_in_bbox(const Params &p, int ray_idx,
         s[i] = cc[i] + tn * dir[i];
         e[i] = cc[i] + tf * dir[i];
     }
+}
+__device__ __forceinline__ void sample_in_bbox(const Params &p, int ray_idx,
+                                               const float *__restrict__ P_inv,
+                                               const float *__restrict__ cc, float s[3],
+                                               float e[3]) {
+    float dir[3];
+    bool misses;
+    pixel_ray(p, ray_idx, P_inv, cc, dir);
+    bbox_segment(p, cc, dir, s, e, misses);
 }
 
 // ------------------------------------------------------------------- a2
@@ -299,19 +315,158 @@ __device__ __forceinline__ void plane_point(const float s[3], const float e[3], 
     for (int a = 0; a < 3; a++) point[a] = s[a] + k * (e[a] - s[a]) / (D - 1);
 }
 
+// ------------------------------------------------ sampling schemes
+// WHERE on the viewing ray the D samples lie.  0 is the box segment above; the other two are
+// the reference's SamplingInRangeScheme / SamplingInDisparityScheme
+// (raynet/common/sampling_schemes.py:178-237 / 240-297).
+constexpr int SCHEME_BBOX = 0, SCHEME_RANGE = 1, SCHEME_DISPARITY = 2;
+constexpr int CAMERA_FLOATS = 28;           // P_pinv [4][3] | centre [4] | P [3][4], row-major
+struct SchemeArgs {                         // a kernel argument: scalar loads
+    int id;
+    float r0, r1;
+    float far_cam[CAMERA_FLOATS];           // sample_in_disparity: the LAST view of the ray's list
+};
+
+// sample_in_range: the segment centre + r0 d^ -> centre + r1 d^, d^ = dir / |dir|; every fp32
+// operation rounded on its own, in this order.  The samples are plane_point(s, e, k, D).
+__device__ __forceinline__ void sample_in_range(const float *__restrict__ cc, const float dir[3],
+                                                float r0, float r1, float s[3], float e[3]) {
+    const float norm = sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const float dh = dir[i] / norm;
+        s[i] = cc[i] + r0 * dh;
+        e[i] = cc[i] + r1 * dh;
+    }
+}
+
+// sample_in_disparity, the per-ray part: both ends of the box segment projected into the far
+// view (fp64 from the fp32 ends on), and what of the closest-point formula does not depend on
+// the plane.
+struct DisparityRay {
+    double c1[3], a1[3];        // the viewing ray: centre, dir
+    double a11, a1p1, a1p2;     // <a1, a1>, <a1, c1>, <a1, c2>
+    double u0, v0, du, dv;      // pixel of p_near in the far view, pixel_far - pixel_near
+    const float *far;           // the far view's camera (CAMERA_FLOATS)
+};
+__device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+}
+__device__ __forceinline__ void disparity_ray(const float *__restrict__ cc, const float dir[3],
+                                              const float s[3], const float e[3],
+                                              const float *__restrict__ far, DisparityRay &d) {
+    const float *P = far + 16;
+    double px[2], py[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const float *x = h ? e : s;
+        double q[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+            q[r] = (((double)P[4 * r] * (double)x[0] + (double)P[4 * r + 1] * (double)x[1]) +
+                    (double)P[4 * r + 2] * (double)x[2]) + (double)P[4 * r + 3];
+        // Image.project rounds to the pixel (common/image.py:80-83, np.round: half to even)
+        px[h] = __builtin_rint(q[0] / q[2]);
+        py[h] = __builtin_rint(q[1] / q[2]);
+    }
+    d.u0 = px[0];
+    d.v0 = py[0];
+    d.du = px[1] - px[0];
+    d.dv = py[1] - py[0];
+    double c2[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        d.c1[i] = (double)cc[i];
+        d.a1[i] = (double)dir[i];
+        c2[i] = (double)far[12 + i];
+    }
+    d.a11 = dot3(d.a1, d.a1);
+    d.a1p1 = dot3(d.a1, d.c1);
+    d.a1p2 = dot3(d.a1, c2);
+    d.far = far;
+}
+// ... and sample k: the pixel at t = linspace(0, 1, D)[k] between the two projections, its ray
+// through the far view's P_pinv, and the point ON THE VIEWING RAY closest to that ray
+// (utils/geometry.py:243-312, first returned point).  fp64 throughout, one rounding to fp32.
+__device__ __forceinline__ void disparity_point(const DisparityRay &d, int k, int D, float point[3]) {
+    const float t = k == D - 1 ? 1.0f : (float)((double)k * (1.0 / (double)(D - 1)));
+    // Image.ray takes the pixel as float32 (common/image.py:237)
+    const double pu = (double)(float)(d.u0 + (double)t * d.du);
+    const double pv = (double)(float)(d.v0 + (double)t * d.dv);
+    const float *Pi = d.far;
+    double o[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+        o[r] = ((double)Pi[3 * r] * pu + (double)Pi[3 * r + 1] * pv) + (double)Pi[3 * r + 2];
+    double a2[3], c2[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        c2[i] = (double)d.far[12 + i];
+        a2[i] = o[i] / o[3] - c2[i];
+    }
+    const double a22 = dot3(a2, a2), a12 = dot3(d.a1, a2);
+    const double a2p1 = dot3(a2, d.c1), a2p2 = dot3(a2, c2);
+    const double div = d.a11 * a22 - a12 * a12;
+    const double t1 = (-a22 * (d.a1p1 - d.a1p2) + a12 * (a2p1 - a2p2)) / div;
+#pragma unroll
+    for (int i = 0; i < 3; i++) point[i] = (float)(d.c1[i] + d.a1[i] * t1);
+}
+
+// One ray of a scheme: the segment (bbox, range) or the disparity construction, and whether the
+// ray has samples at all -- a sample_in_disparity ray that misses the box has none (the
+// reference returns None): its D points are the camera centre with w = 0, finite and flagged.
+struct SchemeRay {
+    float s[3], e[3];
+    DisparityRay d;
+    bool missed;
+};
+template <bool DISP>
+__device__ __forceinline__ void scheme_ray(const Params &p, int id, float r0, float r1, int ray_idx,
+                                           const float *__restrict__ P_inv,
+                                           const float *__restrict__ cc,
+                                           const float *__restrict__ far, SchemeRay &sr) {
+    float dir[3];
+    pixel_ray(p, ray_idx, P_inv, cc, dir);
+    sr.missed = false;
+    if (!DISP && id == SCHEME_RANGE) {
+        sample_in_range(cc, dir, r0, r1, sr.s, sr.e);
+    } else {
+        bool misses;
+        bbox_segment(p, cc, dir, sr.s, sr.e, misses);
+        if (DISP) {
+            sr.missed = misses;
+            disparity_ray(cc, dir, sr.s, sr.e, far, sr.d);
+#pragma unroll
+            for (int i = 0; i < 3; i++) sr.s[i] = sr.e[i] = cc[i];      // what a missed ray samples
+        }
+    }
+}
+template <bool DISP>
+__device__ __forceinline__ void scheme_point(const SchemeRay &sr, int k, int D, float point[3]) {
+    if (DISP && !sr.missed)
+        disparity_point(sr.d, k, D, point);
+    else
+        plane_point(sr.s, sr.e, k, D, point);
+}
+
 // Generic plane sweep: lane = depth plane, the F-long dot is walked serially in
 // the reference's order (pairs i<j, then f), so it tracks the oracle to the
 // last bit before expf.  Any N, any F.  Writes raw pair sums / pairs to Sl[D].
+// DISP: lane k's point comes from the ray's sample_in_disparity construction (scheme_point)
+// instead of the segment s -> e.
+template <bool DISP = false>
 __device__ __forceinline__ void sweep_generic(const Params &p, const FeatureViews &fv,
                                               const float *const *__restrict__ tbl,
                                               const float *__restrict__ P, const float s[3],
-                                              const float e[3], int lane, float *Sl) {
+                                              const float e[3], int lane, float *Sl,
+                                              const SchemeRay *sr = nullptr) {
     const int pairs = (p.N * (p.N - 1)) / 2;
     for (int base = 0; base < p.D; base += WAVE) {
         const int k = base + lane;
         if (k < p.D) {
             float point[3];
-            plane_point(s, e, k, p.D, point);
+            if (DISP) scheme_point<true>(*sr, k, p.D, point);
+            else plane_point(s, e, k, p.D, point);
             float acc = 0.0f;
             for (int i = 0; i < p.N; i++) {
                 const float *fi = (tbl ? tbl[i] : fv.v[i]) + feature_offset(p, P + 12 * i, point);
@@ -470,11 +625,14 @@ __device__ __forceinline__ float sweep_rounds(const float *const (&vbase)[NV], c
 // segment in ITS s / e; ray q's column goes to Sl[q * D ...]; `nrays` of them exist (the lanes of
 // a missing ray shadow the last one).  The arithmetic per (ray, plane) sample is the same
 // instruction sequence either way: the columns are the same bits.
-template <int NV, int LPS, bool FAST = false, int RPW = 1>
+// DISP (RPW = 1): lane k constructs its own sample_in_disparity point, once per plane.
+template <int NV, int LPS, bool FAST = false, int RPW = 1, bool DISP = false>
 __device__ __forceinline__ void sweep_coop(const Params &p, const FeatureViews &fv,
                                            const float *const *__restrict__ tbl,
                                            const float *__restrict__ P, const float s[3],
-                                           const float e[3], int lane, float *Sl, int nrays = 1) {
+                                           const float e[3], int lane, float *Sl, int nrays = 1,
+                                           const SchemeRay *sr = nullptr) {
+    static_assert(!DISP || RPW == 1, "the schemes sweep one ray per wavefront");
     constexpr int SPL = WAVE / LPS;       // planes per load round
     constexpr int V4 = SWEEP_V4;          // float4s per lane and view
     constexpr int DPAD = WAVE / RPW;      // lanes (= plane slots) per ray
@@ -496,7 +654,8 @@ __device__ __forceinline__ void sweep_coop(const Params &p, const FeatureViews &
         {
             const int k = min(RPW == 1 ? base + lane : lane % DPAD, p.D - 1);
             float point[3];
-            plane_point(s, e, k, p.D, point);
+            if (DISP) scheme_point<true>(*sr, k, p.D, point);
+            else plane_point(s, e, k, p.D, point);
             // The 12 entries of a view's matrix are wave-uniform: scalar loads into SGPRs.  (While
             // the class test below went through ballot(bool) the compiler hoisted all NV x 12 of
             // them out of the chunk loop and at 9 views spilled 125 SGPRs, ~300 v_writelane /

@@ -20,6 +20,9 @@ struct rn_ctx {
     // rn_batch_rays / rn_batch_patches: "an index was out of range" (device word, pinned mirror),
     // allocated by the first such call
     int32_t *batch_bad = nullptr, *batch_bad_host = nullptr;
+    // sample_in_range's ray segments between k_range_segments and the plane sweep: [2][rays][3]
+    float *range_seg = nullptr;
+    size_t range_seg_rays = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // slab boxes (rn_scene_bind_slab_boxes): table, the list buffer it describes, and the row
     // range rn_scene_prepare_all last filled
@@ -278,6 +281,83 @@ void launch_sweep(rn_ctx *ctx, const SweepArgs &a, bool have_features, hipStream
             });
         });
     if (!cooperative) launch_sweep_t<1, 1, 8, MAPMODE, PACKED>(ctx, a, st);
+}
+
+// ---- sampling schemes (include/raynet_hip.h, "sampling schemes") ----
+// the host POD checked and turned into the kernels' argument; RN_OK or a recorded failure
+int scheme_args(rn_ctx *ctx, const rn_sampling *sm, const char *what, SchemeArgs &sa) {
+    if (!sm) return fail(ctx, RN_ERR_INVALID, "%s: sampling is required", what);
+    if (sm->scheme != RN_SAMPLE_IN_BBOX && sm->scheme != RN_SAMPLE_IN_RANGE &&
+        sm->scheme != RN_SAMPLE_IN_DISPARITY)
+        return fail(ctx, RN_ERR_INVALID, "%s: unknown sampling scheme %d", what, (int)sm->scheme);
+    if (ctx->p.D < 2) return fail(ctx, RN_ERR_INVALID, "%s: D = %d, a scheme needs D >= 2", what, ctx->p.D);
+    const float r0 = sm->range[0], r1 = sm->range[1];
+    if (sm->scheme == RN_SAMPLE_IN_RANGE && !(r0 > 0.0f && r0 < r1 && r1 < INFINITY))
+        return fail(ctx, RN_ERR_INVALID, "%s: depth range (%g, %g) is not 0 < r0 < r1 < infinity",
+                    what, (double)r0, (double)r1);
+    sa.id = sm->scheme;
+    sa.r0 = r0;
+    sa.r1 = r1;
+    for (int i = 0; i < 12; i++) {
+        sa.far_cam[i] = sm->far_P_inv[i];
+        sa.far_cam[16 + i] = sm->far_P[i];
+    }
+    for (int i = 0; i < 4; i++) sa.far_cam[12 + i] = sm->far_centre[i];
+    return RN_OK;
+}
+
+// K9 / K10 under sample_in_disparity: cooperative for F = 32 and 2..9 views, generic otherwise;
+// one ray per wavefront whatever D is
+void launch_sweep_disparity(rn_ctx *ctx, int n, const int32_t *ray_idxs, const float *features,
+                            const float *P, const float *P_inv, const float *cc,
+                            const SchemeArgs &sa, float *Sp, float *depth_map, float *points,
+                            hipStream_t st) {
+    ProfScope prof(ctx, RN_K_SWEEP_MAP, n, st);
+    const FeatureViews fv = stacked_views(ctx->p, features);
+    const size_t lds = sizeof(float) * (size_t)SWEEP_WAVES * ctx->p.D;
+    auto go = [&](auto kernel) {
+        lds_opt_in(ctx, (const void *)kernel, lds);
+        hipLaunchKernelGGL(kernel, dim3(sweep_blocks(n)), dim3(SWEEP_BLOCK), lds, st, ctx->p, n,
+                           ray_idxs, fv, P, P_inv, cc, sa, Sp, depth_map, points);
+    };
+    const bool cooperative = ctx->p.F == 32 && !ctx->generic_sweep &&
+        with_value<2, 3, 4, 5, 6, 7, 8, 9>(ctx->p.N, [&](auto nv) {
+            go(k_sweep_disparity<2, decltype(nv)::value>);
+        });
+    if (!cooperative) go(k_sweep_disparity<1, 1>);
+}
+// K9 / K10 under sample_in_range: the ray's segment (k_range_segments, into a buffer the context
+// keeps), then the plane sweep the old entries run, on segments instead of on pixels -- the same
+// kernels, the packed D <= 32 layout included
+int launch_sweep_range(rn_ctx *ctx, int n, const int32_t *ray_idxs, const float *features,
+                       const float *P, const float *P_inv, const float *cc, const SchemeArgs &sa,
+                       float *Sp, float *depth_map, float *points, hipStream_t st) {
+    if ((size_t)n > ctx->range_seg_rays) {
+        if (ctx->range_seg) RN_HIP(ctx, hipFree(ctx->range_seg));      // (waits for its readers)
+        ctx->range_seg = nullptr;
+        ctx->range_seg_rays = 0;
+        RN_HIP(ctx, hipMalloc(&ctx->range_seg, sizeof(float) * 6 * (size_t)n));
+        ctx->range_seg_rays = (size_t)n;
+    }
+    float *starts = ctx->range_seg, *ends = ctx->range_seg + 3 * (size_t)n;
+    {
+        ProfScope prof(ctx, RN_K_OTHER, n, st);
+        hipLaunchKernelGGL(k_range_segments, dim3(thread_blocks(n)), dim3(BLOCK), 0, st, ctx->p, n,
+                           ray_idxs, P_inv, cc, sa.r0, sa.r1, starts, ends);
+    }
+    SweepArgs a{n, nullptr, stacked_views(ctx->p, features), P, nullptr, cc, starts, ends, nullptr,
+                nullptr, nullptr, Sp, nullptr, depth_map, points};
+    launch_sweep<0, false>(ctx, a, true, st);
+    return RN_OK;
+}
+inline int launch_sweep_scheme(rn_ctx *ctx, int n, const int32_t *ray_idxs, const float *features,
+                               const float *P, const float *P_inv, const float *cc,
+                               const SchemeArgs &sa, float *Sp, float *depth_map, float *points,
+                               hipStream_t st) {
+    if (sa.id == SCHEME_RANGE)
+        return launch_sweep_range(ctx, n, ray_idxs, features, P, P_inv, cc, sa, Sp, depth_map, points, st);
+    launch_sweep_disparity(ctx, n, ray_idxs, features, P, P_inv, cc, sa, Sp, depth_map, points, st);
+    return RN_OK;
 }
 
 // the slab-box rows that describe `vox` (a pointer into the bound list buffer), or null

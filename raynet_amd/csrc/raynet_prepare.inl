@@ -31,6 +31,40 @@ __global__ void k_sample_points(Params p, int n, const int32_t *__restrict__ ray
         row[k] = make_float4(pt[0], pt[1], pt[2], 1.0f);
     }
 }
+// ... with the samples where a sampling scheme puts them (sampling_schemes.py:178-297): one wave
+// per ray, lane k constructs point k.  w = 0 marks a sample_in_disparity ray that misses the box.
+template <bool DISP>
+__global__ void k_sample_points_scheme(Params p, int n, const int32_t *__restrict__ ray_idxs,
+                                       const float *__restrict__ P_inv,
+                                       const float *__restrict__ cc, SchemeArgs sa, float *points) {
+    int lane;
+    const int r = ray_of_wave(n, lane);
+    if (r < 0) return;
+    SchemeRay sr;
+    scheme_ray<DISP>(p, sa.id, sa.r0, sa.r1, ray_idxs[r], P_inv, cc, sa.far_cam, sr);
+    float4 *row = reinterpret_cast<float4 *>(points) + (size_t)r * p.D;
+    for (int k = lane; k < p.D; k += WAVE) {
+        float pt[3];
+        scheme_point<DISP>(sr, k, p.D, pt);
+        row[k] = make_float4(pt[0], pt[1], pt[2], sr.missed ? 0.0f : 1.0f);
+    }
+}
+
+// sample_in_range's segment per ray -> starts / ends [n][3]: what k_sample_rays is to the box
+// segment.  The plane sweep then runs on them as it does for rn_compute_similarities.
+__global__ void k_range_segments(Params p, int n, const int32_t *__restrict__ ray_idxs,
+                                 const float *__restrict__ P_inv, const float *__restrict__ cc,
+                                 float r0, float r1, float *starts, float *ends) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    float dir[3], s[3], e[3];
+    pixel_ray(p, ray_idxs[r], P_inv, cc, dir);
+    sample_in_range(cc, dir, r0, r1, s, e);
+    for (int i = 0; i < 3; i++) {
+        starts[3 * r + i] = s[i];
+        ends[3 * r + i] = e[i];
+    }
+}
 
 // occupancy_to_ray(prior, 0) by the device's own arithmetic (see first_sweep_messages)
 __global__ void k_first_occupancy(float prior, float *out) { out[0] = occupancy_to_ray(prior, 0.0f); }
@@ -685,4 +719,84 @@ void k_sweep_map_packed(
         voxels_out<MAPMODE, PACKED>(p, rq, cq, n_staged, su, eu, Sl + q * p.D, vals, axes, pos, vrow,
                                     S_voxel, msgs_out, o_first, lane);
     }
+}
+
+// ------------------------------------------- plane sweep under a sampling scheme (K9 / K10)
+// planes_out with the per-plane points of a scheme: the column, and for
+// K10 the points, the first arg-max plane and the distance of ITS point to the camera centre.
+template <bool DISP>
+__device__ __forceinline__ void planes_out_scheme(const Params &p, int r, const SchemeRay &sr,
+                                                  const float *Sl, int lane,
+                                                  const float *__restrict__ cc, float *S_planes,
+                                                  float *depth_from_planes, float *points) {
+    for (int k = lane; k < p.D; k += WAVE) S_planes[(size_t)r * p.D + k] = Sl[k];
+    if (!depth_from_planes) return;
+    float best = -INFINITY;
+    int best_k = 0;
+    float best_pt[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = lane; k < p.D; k += WAVE) {
+        float pt[3];
+        scheme_point<DISP>(sr, k, p.D, pt);
+        reinterpret_cast<float4 *>(points)[(size_t)r * p.D + k] =
+            make_float4(pt[0], pt[1], pt[2], sr.missed ? 0.0f : 1.0f);
+        if (Sl[k] > best) {
+            best = Sl[k];
+            best_k = k;
+#pragma unroll
+            for (int i = 0; i < 3; i++) best_pt[i] = pt[i];
+        }
+    }
+    // first maximum: larger value wins, then smaller index; its point travels with it
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int ok = __shfl_xor(best_k, o);
+        float opt[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) opt[i] = __shfl_xor(best_pt[i], o);
+        if (ob > best || (ob == best && ok < best_k)) {
+            best = ob;
+            best_k = ok;
+#pragma unroll
+            for (int i = 0; i < 3; i++) best_pt[i] = opt[i];
+        }
+    }
+    if (lane == 0) {
+        // a lane that never saw a value above -inf (a NaN column) holds plane 0's index only
+        if (!(best > -INFINITY)) scheme_point<DISP>(sr, 0, p.D, best_pt);
+        float sum = 0.0f;
+        for (int i = 0; i < 3; i++) {
+            const float d = best_pt[i] - cc[i];
+            sum += d * d;
+        }
+        depth_from_planes[r] = sqrtf(sum);
+    }
+}
+
+// k_sweep_map's MAPMODE 0 for sample_in_disparity, one ray per wavefront (also for D <= 32: the
+// packed layout is not offered to it).  SIM 1: generic sweep, 2: cooperative (F = 32, N = NV).
+// Lane k constructs its point in fp64, once per plane and chunk.  (sample_in_range needs no
+// kernel of its own: k_range_segments, then k_sweep_map on the segments.)
+// Dynamic LDS: per wave the D plane column.
+template <int SIM, int NV>
+__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_disparity(
+    Params p, int n, const int32_t *__restrict__ ray_idxs, FeatureViews fv,
+    const float *__restrict__ P, const float *__restrict__ P_inv, const float *__restrict__ cc,
+    SchemeArgs sa, float *S_planes, float *depth_from_planes, float *points) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *Sl = smem + (threadIdx.x >> 6) * p.D;
+    int lane;
+    const int r = ray_of_wave<SWEEP_BLOCK, XCD_CHUNK_SWEEP>(n, lane);
+    if (r < 0) return;
+    constexpr bool DISP = true;
+    SchemeRay sr;
+    scheme_ray<DISP>(p, sa.id, sa.r0, sa.r1, ray_idxs[r], P_inv, cc, sa.far_cam, sr);
+    if (SIM == 1)
+        sweep_generic<DISP>(p, fv, nullptr, P, sr.s, sr.e, lane, Sl, &sr);
+    else
+        sweep_coop<NV, 8 / SWEEP_V4, false, 1, DISP>(p, fv, nullptr, P, sr.s, sr.e, lane, Sl, 1, &sr);
+    wave_sync();
+    softmax_column<false>(p.D, lane, Sl);
+    wave_sync();
+    planes_out_scheme<DISP>(p, r, sr, Sl, lane, cc, S_planes, depth_from_planes, points);
 }

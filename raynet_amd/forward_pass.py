@@ -38,6 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .common.sampling_schemes import far_view_of
 from .hip_implementations.options import PathOptions, shard_alpha_for
 from .hip_implementations.mvcnn_with_ray_marching_and_voxels_mapping import \
     batch_mvcnn_voxel_traversal_with_ray_marching_with_depth_estimation
@@ -152,11 +153,16 @@ def shard_bounds(n, rank, world):
 
 class ForwardPass(object):
     """forward_pass.py:25-223."""
+    SAMPLING_SCHEMES = ("sample_in_bbox",)
 
     def __init__(self, model, generation_params, sampling_scheme, image_shape,
                  rays_batch=50000, filter_out_rays=False):
         self._model = model
         self._generation_params = generation_params
+        if sampling_scheme not in self.SAMPLING_SCHEMES:
+            # the voxel-space paths traverse the box segment and map evenly spaced planes on it
+            # to voxels: sample_in_bbox only
+            raise NotImplementedError(sampling_scheme)
         self._sampling_scheme = sampling_scheme
         self.rays_batch = rays_batch
         self._filter_out_rays = filter_out_rays
@@ -205,7 +211,10 @@ class ForwardPass(object):
 
 
 class MultiViewCNNForwardPass(ForwardPass):
-    """forward_pass.py:226-344 (kernel K10)."""
+    """forward_pass.py:226-344 (kernel K10).  The sampling scheme only decides where on the ray
+    the D samples lie: sample_in_range takes generation_params.depth_range, sample_in_disparity
+    the last view of the reference image's neighbour list."""
+    SAMPLING_SCHEMES = ("sample_in_bbox", "sample_in_range", "sample_in_disparity")
 
     def forward_pass(self, scene, images_range):
         assert isinstance(images_range, tuple)
@@ -222,8 +231,11 @@ class MultiViewCNNForwardPass(ForwardPass):
             if self._fp is None:
                 self._fp = perform_multi_view_cnn_forward_pass_with_depth_estimation(
                     gp.depth_planes, gp.neighbors + 1, F, H, W, gp.padding, scene.bbox.ravel(),
-                    self._sampling_scheme)
+                    self._sampling_scheme, gp.depth_range)
             ctx = self._fp.context
+            more = {}
+            if self._sampling_scheme == "sample_in_disparity":
+                more["far_view"] = far_view_of(images)
             P, P_inv, center = (ctx.dev(a) for a in self._camera_arrays(images))
             # The reference uploads the ray list and allocates zero-filled S / points per image
             # (forward_pass.py:283-300).  K10 writes every entry of the rows it is handed, so the
@@ -246,7 +258,8 @@ class MultiViewCNNForwardPass(ForwardPass):
             s, pts = buf["s"], buf["pts"]
             depth_map = torch.zeros((H * W,), dtype=torch.float32, device=ctx.device)
             for i in range(0, len(ridx), nb):
-                self._fp(ridx[i:i + nb], features, P, P_inv, center, s, pts, depth_map[i:i + nb])
+                self._fp(ridx[i:i + nb], features, P, P_inv, center, s, pts, depth_map[i:i + nb],
+                         **more)
             ref_idx += skip
             yield depth_map.cpu().numpy().reshape(W, H).T
 

@@ -433,11 +433,13 @@ class HipContext(object):
         return V, N
 
     def batch_rays(self, view, ray_idxs, depth, cams, nbr, patch_shape, points, target, centres,
-                   flags):
+                   flags, sampling=None):
         """rn_batch_rays: n candidate rays, each of its own reference view, in one launch.
         view, ray_idxs [n] i32, depth [n] f32, cams (V, 28) f32, nbr (V, N) i32 -> points
         [n, D, 4], target [n, 4], centres [n, N, D, 2] i32, flags [n] i32 (0 = valid).  An index
-        out of range raises (the entry decides it from the kernel's own tests and synchronises)."""
+        out of range raises (the entry decides it from the kernel's own tests and synchronises).
+        sampling: an rn_sampling POD (HipContext.sampling) -> rn_batch_rays_scheme; the far view of
+        sample_in_disparity is cams[nbr[view][N - 1]], the POD's is not read."""
         n = len(ray_idxs)
         V, N = self._chk_batch_tables(view, nbr, n)
         h, w = int(patch_shape[0]), int(patch_shape[1])
@@ -454,6 +456,12 @@ class HipContext(object):
         _chk(target, torch.float32, n * 4, "target", align=16)
         _chk(centres, torch.int32, n * N * self.D * 2, "centres", align=8)
         _chk(flags, torch.int32, n, "flags")
+        if sampling is not None:
+            self._check(self.lib.rn_batch_rays_scheme(
+                self._h, n, _ptr(view), _ptr(ray_idxs), _ptr(depth), _ptr(cams), V, _ptr(nbr), N, h,
+                w, ctypes.byref(sampling), _ptr(points), _ptr(target), _ptr(centres), _ptr(flags),
+                _stream()))
+            return
         self._check(self.lib.rn_batch_rays(self._h, n, _ptr(view), _ptr(ray_idxs), _ptr(depth),
                                            _ptr(cams), V, _ptr(nbr), N, h, w, _ptr(points),
                                            _ptr(target), _ptr(centres), _ptr(flags), _stream()))
@@ -647,6 +655,73 @@ class HipContext(object):
         self._check(self.lib.rn_mvcnn_depth(self._h, len(ray_idxs), _ptr(ray_idxs), _ptr(features),
                                             _ptr(P), _ptr(P_inv), _ptr(center), _ptr(S),
                                             _ptr(points), _ptr(depth_map), _stream()))
+
+    # -- K8 / K9 / K10 and the batch assembler under a sampling scheme (rn_sampling) ---------
+    @staticmethod
+    def sampling(scheme="sample_in_bbox", depth_range=None, far_view=None, far_from_table=False):
+        """The rn_sampling POD.  scheme: a name of _lib.SAMPLING_SCHEMES (or its id);
+        depth_range (r0, r1) for sample_in_range; far_view = (P 3x4, P_pinv 4x3, centre) of the
+        LAST view of the ray's neighbour list for sample_in_disparity (host arrays) --
+        far_from_table: for batch_rays, which reads it out of its camera table."""
+        sm = _lib.Sampling()
+        if isinstance(scheme, str):
+            if scheme not in _lib.SAMPLING_SCHEMES:
+                raise NotImplementedError(scheme)
+            scheme = _lib.SAMPLING_SCHEMES[scheme]
+        sm.scheme = int(scheme)
+        if sm.scheme == _lib.SAMPLING_SCHEMES["sample_in_range"] and depth_range is None:
+            raise ValueError("sample_in_range needs a depth_range (r0, r1)")
+        if depth_range is not None:
+            sm.range[0], sm.range[1] = float(depth_range[0]), float(depth_range[1])
+        if sm.scheme == _lib.SAMPLING_SCHEMES["sample_in_disparity"] and far_view is None \
+                and not far_from_table:
+            raise ValueError("sample_in_disparity needs the far view (P, P_pinv, centre)")
+        if far_view is not None:
+            P, P_inv, centre = (np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a,
+                                           np.float32).ravel() for a in far_view)
+            if P.size != 12 or P_inv.size != 12 or centre.size not in (3, 4):
+                raise ValueError("far_view: (P 3x4, P_pinv 4x3, centre 3 or 4)")
+            sm.far_P[:] = P.tolist()
+            sm.far_P_inv[:] = P_inv.tolist()
+            sm.far_centre[:] = (centre.tolist() + [1.0])[:4]
+        return sm
+
+    def sample_points_scheme(self, ray_idxs, P_inv, center, sampling, points):
+        n = len(ray_idxs)
+        _chk(ray_idxs, torch.int32, n, "ray_idxs")
+        _chk(P_inv, torch.float32, 12, "P_inv")
+        _chk(center, torch.float32, 3, "center")
+        _chk(points, torch.float32, n * self.D * 4, "points", align=16)
+        self._check(self.lib.rn_sample_points_scheme(self._h, n, _ptr(ray_idxs), _ptr(P_inv),
+                                                     _ptr(center), ctypes.byref(sampling),
+                                                     _ptr(points), _stream()))
+
+    def _chk_sweep(self, n, ray_idxs, features, P, P_inv, center, S):
+        _chk(ray_idxs, torch.int32, n, "ray_idxs")
+        _chk(features, torch.float32,
+             self.N * (self.H + self.padding + 1) * (self.W + self.padding + 1) * self.F, "features",
+             align=16)
+        _chk(P, torch.float32, 12 * self.N, "P")
+        _chk(P_inv, torch.float32, 12, "P_inv")
+        _chk(center, torch.float32, 3, "center")
+        _chk(S, torch.float32, n * self.D, "S")
+
+    def mvcnn_similarities_scheme(self, ray_idxs, features, P, P_inv, center, sampling, S):
+        n = len(ray_idxs)
+        self._chk_sweep(n, ray_idxs, features, P, P_inv, center, S)
+        self._check(self.lib.rn_mvcnn_similarities_scheme(
+            self._h, n, _ptr(ray_idxs), _ptr(features), _ptr(P), _ptr(P_inv), _ptr(center),
+            ctypes.byref(sampling), _ptr(S), _stream()))
+
+    def mvcnn_depth_scheme(self, ray_idxs, features, P, P_inv, center, sampling, S, points,
+                           depth_map):
+        n = len(ray_idxs)
+        self._chk_sweep(n, ray_idxs, features, P, P_inv, center, S)
+        _chk(points, torch.float32, n * self.D * 4, "points", align=16)
+        _chk(depth_map, torch.float32, n, "depth_map")
+        self._check(self.lib.rn_mvcnn_depth_scheme(
+            self._h, n, _ptr(ray_idxs), _ptr(features), _ptr(P), _ptr(P_inv), _ptr(center),
+            ctypes.byref(sampling), _ptr(S), _ptr(points), _ptr(depth_map), _stream()))
 
     def mvcnn_voxel_space(self, ray_idxs, features, P, P_inv, center, rvi, rvc, S_voxel,
                           depth_map=None):

@@ -25,6 +25,10 @@ def _ints(x):
     return tuple(map(int, x.split(",")))
 
 
+def _floats(x):
+    return tuple(map(float, x.split(",")))
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=("Do a forward pass and estimate the per pixel depth "
                                              "for the images of a scene"))
@@ -44,6 +48,13 @@ def build_parser():
     p.add_argument("--neighbors", type=int, default=4)
     p.add_argument("--grid_shape", type=_ints, default="256,256,128")
     p.add_argument("--maximum_number_of_marched_voxels", type=int, default=650)
+    p.add_argument("--sampling_policy",
+                   choices=["sample_in_bbox", "sample_in_range", "sample_in_disparity"],
+                   default="sample_in_bbox",
+                   help="Where on the viewing ray the depth planes lie (multi_view_cnn factory; "
+                        "the voxel-space factories sample in the bounding box only)")
+    p.add_argument("--depth_range", type=_floats, default="3.0,7.0",
+                   help="The depth range used when sampling planes in range")
     # :302-329 (dataset)
     p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
                    default="filesystem")
@@ -85,6 +96,10 @@ def main(argv=None):
     if args.depth_statistics and (args.forward_pass_factory != "raynet" or
                                   args.schedule != "resident"):
         parser.error("--depth_statistics needs --forward_pass_factory raynet --schedule resident")
+    if args.sampling_policy != "sample_in_bbox" and args.forward_pass_factory != "multi_view_cnn":
+        parser.error("--sampling_policy %s needs --forward_pass_factory multi_view_cnn: the "
+                     "voxel-space factories (%s) march the voxels of the bounding-box segment"
+                     % (args.sampling_policy, args.forward_pass_factory))
     import torch
     from raynet_amd.common.generation_parameters import GenerationParameters
     from raynet_amd.common.scene import get_scene
@@ -98,6 +113,8 @@ def main(argv=None):
         args.grid_shape = _ints(args.grid_shape)
     if isinstance(args.start_end, str):
         args.start_end = _ints(args.start_end)
+    if isinstance(args.depth_range, str):
+        args.depth_range = _floats(args.depth_range)
     args.grid_shape = np.array(args.grid_shape, dtype=np.int32)
     generation_params = GenerationParameters.from_options(args)
 
@@ -117,7 +134,8 @@ def main(argv=None):
     if args.forward_pass_factory == "raynet":
         kwargs["bp_iterations"] = args.bp_iterations
         kwargs["schedule"] = args.schedule
-    fp = cls(model, generation_params, "sample_in_bbox", scene.image_shape, args.rays_batch, **kwargs)
+    fp = cls(model, generation_params, args.sampling_policy, scene.image_shape, args.rays_batch,
+             **kwargs)
 
     start, end = args.start_end
     ref_idx = start

@@ -68,6 +68,11 @@ def main(argv=None):
     if args.network_architecture not in ["simple_cnn"]:          # (as the reference, :158)
         raise ValueError("Expected argument %r but received %r"
                          % (["simple_cnn"], args.network_architecture))
+    if args.sampling_policy != "sample_in_bbox":
+        raise NotImplementedError(
+            "--sampling_policy %s: end-to-end training marches the voxels of the bounding-box "
+            "segment and maps evenly spaced planes on it to them, so it samples in the bounding "
+            "box only; pretrain_network takes the other policies" % args.sampling_policy)
     from raynet_amd.scripts.forward_pass import load_model
     from raynet_amd.train_network.ray_sampler import RayBatchSampler, SceneBank
     from raynet_amd.train_network.trainer import Trainer, draw_validation_set

@@ -20,6 +20,7 @@ import collections
 import numpy as np
 import torch
 
+from ..common.sampling_schemes import scheme_name
 from ..hip_implementations import get_context
 from .raynet_batch_provider import one_hot_target
 
@@ -74,6 +75,12 @@ class SceneEntry(object):
         self.voxel_grid = self.hip.dev(vg)
         self.bbox = torch.from_numpy(bbox).to(dev)
         self.grid = torch.tensor(grid, dtype=torch.float32, device=dev)
+        # where on the ray the D samples lie: generation_params.sampling_type (None: the box
+        # segment, through rn_batch_rays itself)
+        name = scheme_name(gp)
+        self.sampling_scheme = name
+        self.sampling = None if name == "sample_in_bbox" else \
+            self.hip.sampling(name, getattr(gp, "depth_range", None), far_from_table=True)
 
 
 class SceneBank(object):
@@ -131,7 +138,7 @@ def evaluate_rays(entry, view, ray_idxs, patch_shape):
     flags = torch.empty((n,), dtype=torch.int32, device=dev)
     if n:
         hip.batch_rays(view, ray_idxs, depth.contiguous(), entry.cams, entry.nbr, patch_shape,
-                       points, target, centres, flags)
+                       points, target, centres, flags, sampling=getattr(entry, "sampling", None))
     return points, target, centres, flags
 
 
@@ -182,6 +189,13 @@ class RayBatchSampler(object):
         if mode not in self.MODES:
             raise ValueError("mode: one of %s, got %r" % (self.MODES, mode))
         self.bank, self.batch_size, self.mode = bank, int(batch_size), mode
+        self.sampling_scheme = scheme_name(bank.gp)
+        if mode != "pretrain" and self.sampling_scheme != "sample_in_bbox":
+            # the end-to-end batches go through the voxel traversal of the box segment and the
+            # planes -> voxels mapping of evenly spaced planes on it
+            raise NotImplementedError(
+                "%s: the end-to-end (voxel-space) batches are sample_in_bbox only; the other "
+                "schemes serve mode 'pretrain'" % self.sampling_scheme)
         n_scenes = bank.dataset.n_scenes
         self.scenes_range = list(range(n_scenes)) if scenes_range is None else list(scenes_range)
         if not self.scenes_range:
