@@ -808,6 +808,42 @@ int rn_batch_rays_scheme(rn_ctx *ctx, int32_t n, const int32_t *view, const int3
                          const rn_sampling *sampling, float *points, float *target,
                          int32_t *centres, int32_t *flags, void *stream);
 
+/* ---- the occupancy volume: what the MRF believes about every voxel ----
+ *
+ * belief_out [gx][gy][gz] f32: belief = occupancy_to_ray(bias + acc[voxel], 0), the occupancy
+ * k_bp / k_depth read for a voxel whose ray sends no message -- the same device function, the
+ * clamp to [1e-4, fl32(1 - 1e-4)] included.  acc: bricked != 0, the resident path's 4x4x4-bricked
+ * buffer of rn_acc_size() floats (the padding voxels of partial bricks are never read); bricked
+ * == 0, the [gx][gy][gz] array.  bias: the prior where the accumulator holds the sums of the
+ * messages only (the plan path without fixed-point sums), else 0.  One pass over the grid.  A NULL
+ * pointer or a `bricked` other than 0 / 1 is RN_ERR_INVALID, no launch. */
+int rn_occupancy_grid(rn_ctx *ctx, const float *acc, int32_t bricked, float bias,
+                      float *belief_out, void *stream);
+
+/* A belief grid seen along n ray segments.  ray_start / ray_end [n][3] as rn_sample_rays and the
+ * scheme entries write them; belief [gx][gy][gz] f32 with values in [0, 1] (rn_occupancy_grid's);
+ * camera_center [3].  The voxels v_0 .. v_{c-1} of a ray are the list rn_voxel_traversal emits for
+ * its segment in this context (same DDA, capped at the context's M; never written to memory).
+ * In fp32, every operation rounded on its own, in this order:
+ *     o_i = belief[v_i];  T_0 = 1;  w_i = o_i T_i;  T_{i+1} = T_i (1 - o_i)
+ *     t_i = sqrt(((x - cx)^2 + (y - cy)^2) + (z - cz)^2), (x, y, z) the centre of v_i
+ *           (rn_set_voxel_grid's axis tables): the depth arithmetic of rn_scene_depth
+ *     i*  = the first i whose w_i is greater than every earlier w (strictly; i = 0 qualifies)
+ * out[plane * out_stride + ray], out_stride >= n, nothing written at or beyond a plane's n-th
+ * entry:
+ *     0 depth           t_{i*}
+ *     1 opacity         1 - T_c
+ *     2 expected depth  (sum_i w_i t_i) / (sum_i w_i), both sums in list order from 0, one IEEE
+ *                       division (0 where sum_i w_i is not positive)
+ *     3 confidence      w_{i*}
+ *     4 median depth    t_i of the first i with T_{i+1} <= 0.5, 0 where no i has
+ * A ray with c = 0 (it misses the box, or its first cell lies outside the grid) has 0 in every
+ * plane.  n == 0: RN_OK, no launch.  n < 0, a NULL pointer or out_stride < n: RN_ERR_INVALID,
+ * no launch.  rn_set_voxel_grid must have been called (RN_ERR_STATE). */
+int rn_volume_render(rn_ctx *ctx, int32_t n, const float *ray_start, const float *ray_end,
+                     const float *camera_center, const float *belief, float *out,
+                     int64_t out_stride, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

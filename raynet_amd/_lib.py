@@ -41,7 +41,9 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_prepare.inl"), os.path.join(CSRC, "raynet_mrf.inl"),
             os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"),
             os.path.join(CSRC, "raynet_mesh.inl"), os.path.join(CSRC, "raynet_filters.inl"),
-            os.path.join(CSRC, "raynet_cloud.inl"), os.path.join(CSRC, "raynet_batch.inl"), HEADER]
+            os.path.join(CSRC, "raynet_cloud.inl"), os.path.join(CSRC, "raynet_batch.inl"),
+            os.path.join(CSRC, "raynet_volume.inl"), os.path.join(CSRC, "raynet_volume_args.h"),
+            HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
         # RAYNET_HIP_LIB names ANOTHER build of the library (a variant somebody made on purpose):
@@ -201,6 +203,8 @@ SIGNATURES = {
     "rn_mvcnn_depth_scheme": [_P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(Sampling), _P, _P, _P, _P],
     "rn_batch_rays_scheme": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, ctypes.POINTER(Sampling),
                              _P, _P, _P, _P, _P],
+    "rn_occupancy_grid": [_P, _P, _I, _F, _P, _P],
+    "rn_volume_render": [_P, _I, _P, _P, _P, _P, _P, _L, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

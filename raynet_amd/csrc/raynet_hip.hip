@@ -1230,3 +1230,6 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 
 // training batches of rays from many reference views
 #include "raynet_batch.inl"
+
+// the occupancy volume: belief grid of an accumulator, rendered along rays
+#include "raynet_volume.inl"

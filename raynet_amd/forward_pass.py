@@ -410,6 +410,22 @@ class RayNetForwardPass(ForwardPass):
     def accumulator(self, value):
         self._acc_grid, self._acc_flat, self._acc_bias = value, None, 0.0
 
+    def occupancy_volume(self):
+        """The last pass's occupancy probabilities as a volume.OccupancyVolume: per voxel the
+        occupancy a ray of a further BP iteration would read (rn_occupancy_grid), in one pass from
+        the bricked sums plus the prior (resident schedule) or from the grid (reference schedule).
+        With a process group the accumulator is the same on every rank after the exchange: any
+        rank may ask."""
+        from .volume import OccupancyVolume
+        if self._ctx is None or (self._acc_flat is None and self._acc_grid is None):
+            raise RuntimeError("occupancy_volume() needs a finished forward pass: this object has "
+                               "not run one yet (iterate forward_pass(scene, images_range) first)")
+        if self._acc_flat is not None:
+            belief = self._ctx.occupancy_grid(self._acc_flat, True, self._acc_bias)
+        else:
+            belief = self._ctx.occupancy_grid(self._acc_grid, False, 0.0)
+        return OccupancyVolume(belief, self._ctx.bbox, self._ctx.grid_shape)
+
     # -- helpers -----------------------------------------------------------
     def _rows_M(self):
         """Row length of the resident buffers (see _row_stride)."""

@@ -284,6 +284,37 @@ class HipContext(object):
         self._check(self.lib.rn_acc_from_grid(self._h, _ptr(grid), _ptr(out), _stream()))
         return out
 
+    # ---- the occupancy volume (raynet_amd/volume.py) --------------------------------------
+    def occupancy_grid(self, acc, bricked, bias=0.0, out=None):
+        """rn_occupancy_grid: -> belief [gx][gy][gz] f32 = occupancy_to_ray(bias + acc, 0) per
+        voxel.  acc: the bricked buffer of acc_size() floats (bricked=True) or the [gx][gy][gz]
+        array (bricked=False)."""
+        _chk(acc, torch.float32, self.acc_size() if bricked else self.G, "accumulator")
+        if out is None:
+            out = torch.empty(self.grid_shape, dtype=torch.float32, device=acc.device)
+        _chk(out, torch.float32, self.G, "belief")
+        self._check(self.lib.rn_occupancy_grid(self._h, _ptr(acc), 1 if bricked else 0,
+                                               float(bias), _ptr(out), _stream()))
+        return out
+
+    def volume_render(self, starts, ends, center, belief, out):
+        """rn_volume_render: starts / ends (n, 3), center [3], belief [gx][gy][gz] -> out
+        (5, S >= n) f32: depth, opacity, expected depth, confidence, median depth; ray i at
+        out[:, i], nothing written at out[:, n:]."""
+        n = len(starts)
+        _chk(starts, torch.float32, 3 * n, "starts")
+        _chk(ends, torch.float32, 3 * n, "ends")
+        _chk(center, torch.float32, 3, "center")
+        _chk(belief, torch.float32, self.G, "belief")
+        _chk(out, torch.float32, 5 * n, "out")
+        if len(ends) != n or out.dim() != 2 or out.shape[0] != 5 or out.shape[1] < n:
+            raise ValueError("ends (%d, 3) and out (5, >= %d): got %s, %s"
+                             % (n, n, tuple(ends.shape), tuple(out.shape)))
+        self._check(self.lib.rn_volume_render(self._h, n, _ptr(starts), _ptr(ends), _ptr(center),
+                                              _ptr(belief), _ptr(out), int(out.shape[1]),
+                                              _stream()))
+        return out
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

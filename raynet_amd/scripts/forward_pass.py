@@ -13,6 +13,8 @@ side; HDF5 itself cannot be read in this image -- or a torch state_dict of the t
 --depth_statistics (raynet factory, resident schedule) writes `confidence_%03d.npy`,
 `expected_depth_%03d.npy` and `depth_std_%03d.npy` of the same shape next to each of them: what
 the model's depth distribution says about the pixel (forward_pass.DepthStatistics).
+--save_occupancy (raynet factory) writes `occupancy.npz`: the occupancy probability of every voxel
+after the pass, with the bounding box and the grid shape (volume.OccupancyVolume).
 """
 import argparse
 import os
@@ -74,7 +76,16 @@ def build_parser():
     p.add_argument("--depth_statistics", action="store_true",
                    help="raynet factory: also write confidence_%%03d.npy, expected_depth_%%03d.npy "
                         "and depth_std_%%03d.npy per reference image")
+    p.add_argument("--save_occupancy", action="store_true",
+                   help="raynet factory: also write occupancy.npz, the occupancy probability of "
+                        "every voxel after the pass (raynet_amd.volume.OccupancyVolume; "
+                        "raynet_amd.scripts.render_volume reads it)")
     return p
+
+
+def _rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 def load_model(weight_file=None, architecture="simple_cnn", in_channels=3, device="cuda"):
@@ -96,6 +107,9 @@ def main(argv=None):
     if args.depth_statistics and (args.forward_pass_factory != "raynet" or
                                   args.schedule != "resident"):
         parser.error("--depth_statistics needs --forward_pass_factory raynet --schedule resident")
+    if args.save_occupancy and args.forward_pass_factory != "raynet":
+        parser.error("--save_occupancy needs --forward_pass_factory raynet: only the MRF keeps an "
+                     "occupancy per voxel (%s estimates depth per ray)" % args.forward_pass_factory)
     if args.sampling_policy != "sample_in_bbox" and args.forward_pass_factory != "multi_view_cnn":
         parser.error("--sampling_policy %s needs --forward_pass_factory multi_view_cnn: the "
                      "voxel-space factories (%s) march the voxels of the bounding-box segment"
@@ -153,6 +167,9 @@ def main(argv=None):
                 np.save(os.path.join(args.output_directory, "%s_%03d.npy" % (name, ref_idx)),
                         getattr(stats, name))
         ref_idx += args.skip_every + 1
+    if args.save_occupancy and _rank() == 0:
+        # (the accumulator is the same on every rank after the exchange: one rank writes)
+        fp.occupancy_volume().save(os.path.join(args.output_directory, "occupancy.npz"))
     return 0
 
 

@@ -1,0 +1,130 @@
+"""The occupancy volume of the MRF: what the model believes about every voxel after a pass.
+
+`RayNetForwardPass.occupancy_volume()` hands it out; here it is saved, loaded, turned into the
+point cloud of its occupied voxels and rendered from any camera -- a reference image of the pass,
+a held-out view, a camera that has no image at all.  The belief grid and
+the rendering are HIP kernels (csrc/raynet_volume.inl, rn_occupancy_grid / rn_volume_render); the
+voxel cloud is one pass of torch operations over the grid.
+"""
+import numpy as np
+import torch
+
+from .common.scene import get_voxel_grid
+
+MAX_M = 1024        # rn_create's limit on the steps of a ray
+
+
+class VolumeRender(object):
+    """What `OccupancyVolume.render` returns: five (H, W) float32 maps in the orientation
+    `forward_pass` returns depth maps in.  With o_i the belief of the i-th voxel a pixel's ray
+    crosses, T_i = prod_{j<i} (1 - o_j), w_i = o_i T_i and t_i the distance of the voxel's centre
+    from the camera (include/raynet_hip.h, rn_volume_render) --
+      depth           t of the first voxel with the largest w
+      opacity         1 - T behind the last voxel
+      expected_depth  sum w_i t_i / sum w_i
+      confidence      the largest w
+      median_depth    t of the first voxel behind which T <= 1/2, 0 if the ray never gets there
+    A pixel whose ray crosses no voxel has 0 everywhere."""
+    __slots__ = ("depth", "opacity", "expected_depth", "confidence", "median_depth")
+    FIELDS = __slots__
+
+    def __init__(self, depth, opacity, expected_depth, confidence, median_depth):
+        self.depth, self.opacity, self.expected_depth = depth, opacity, expected_depth
+        self.confidence, self.median_depth = confidence, median_depth
+
+    def __iter__(self):
+        return iter(tuple(getattr(self, f) for f in self.FIELDS))
+
+
+class OccupancyVolume(object):
+    """belief: [gx][gy][gz] float32 occupancy probabilities (array or tensor, host or device);
+    bbox: the 6 numbers of the scene's bounding box; grid_shape: (gx, gy, gz)."""
+
+    KEYS = ("belief", "bbox", "grid_shape")
+
+    def __init__(self, belief, bbox, grid_shape):
+        self.grid_shape = tuple(int(g) for g in np.asarray(grid_shape).ravel())
+        if len(self.grid_shape) != 3 or min(self.grid_shape) < 1:
+            raise ValueError("grid_shape: three positive sizes, got %r" % (grid_shape,))
+        self.bbox = np.ascontiguousarray(np.asarray(bbox, dtype=np.float32).reshape(-1))
+        if self.bbox.shape != (6,):
+            raise ValueError("bbox: 6 numbers, got %r" % (bbox,))
+        if not isinstance(belief, torch.Tensor):
+            belief = torch.from_numpy(np.ascontiguousarray(belief, dtype=np.float32))
+        if belief.dtype != torch.float32 or tuple(belief.shape) != self.grid_shape:
+            raise ValueError("belief: expected float32 of shape %s, got %s of shape %s"
+                             % (self.grid_shape, belief.dtype, tuple(belief.shape)))
+        self.belief = belief.contiguous()
+
+    # ---- file ------------------------------------------------------------------------------
+    def save(self, path):
+        """An .npz of `belief` [gx][gy][gz] f32, `bbox` [6] f32 and `grid_shape` [3] i32."""
+        with open(path, "wb") as f:        # (a file object: savez appends no suffix of its own)
+            np.savez(f, belief=self.belief.cpu().numpy(), bbox=self.bbox,
+                     grid_shape=np.array(self.grid_shape, dtype=np.int32))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            if sorted(z.files) != sorted(cls.KEYS):
+                raise ValueError("%s: expected the arrays %s, found %s"
+                                 % (path, ", ".join(cls.KEYS), ", ".join(sorted(z.files))))
+            return cls(z["belief"], z["bbox"], z["grid_shape"])
+
+    # ---- the occupied voxels ---------------------------------------------------------------
+    def pointcloud(self, threshold=0.5, surface_only=True):
+        """-> raynet_amd.pointcloud.Pointcloud of the centres of the voxels with belief >=
+        threshold, in the grid's [gx][gy][gz] order; surface_only: only those with a 6-neighbour
+        below the threshold or outside the grid."""
+        from .pointcloud import Pointcloud
+        occ = self.belief >= float(threshold)
+        keep = occ
+        if surface_only:
+            padded = torch.nn.functional.pad(occ, (1, 1, 1, 1, 1, 1), value=False)
+            gx, gy, gz = self.grid_shape
+            inner = padded[0:gx, 1:-1, 1:-1] & padded[2:gx + 2, 1:-1, 1:-1] & \
+                padded[1:-1, 0:gy, 1:-1] & padded[1:-1, 2:gy + 2, 1:-1] & \
+                padded[1:-1, 1:-1, 0:gz] & padded[1:-1, 1:-1, 2:gz + 2]
+            keep = occ & ~inner
+        centres = get_voxel_grid(self.bbox, self.grid_shape).reshape(3, -1)
+        return Pointcloud(np.ascontiguousarray(centres[:, keep.reshape(-1).cpu().numpy()]))
+
+    # ---- rendering -------------------------------------------------------------------------
+    def _context(self, image_shape, M):
+        from .hip_implementations import get_context
+        H, W = int(image_shape[0]), int(image_shape[1])
+        if M is None:
+            # a DDA moves monotonically along every axis: at most gx + gy + gz - 2 cells, so no
+            # ray is capped (but for grids beyond the library's limit on a ray's steps)
+            M = min(sum(self.grid_shape), MAX_M)
+        ctx = get_context(M=int(M), H=H, W=W, bbox=self.bbox, grid_shape=self.grid_shape)
+        if not ctx._grid_set:
+            ctx.set_voxel_grid(np.ascontiguousarray(
+                get_voxel_grid(self.bbox, self.grid_shape).transpose(1, 2, 3, 0)))
+        return ctx
+
+    def render(self, camera, image_shape, M=None):
+        """The volume seen from `camera` (common.camera.Camera: P_pinv, center) at every pixel of
+        an (H, W) image -> VolumeRender.  The rays are `sample_rays`' box segments; M: the cap on
+        a ray's voxels (default: none that can bind)."""
+        ctx = self._context(image_shape, M)
+        H, W = ctx.H, ctx.W
+        n = H * W
+        dev = ctx.device
+        ridx = torch.arange(n, dtype=torch.int32, device=dev)
+        P_inv = ctx.dev(np.ascontiguousarray(camera.P_pinv, dtype=np.float32))
+        center = ctx.dev(np.ascontiguousarray(camera.center, dtype=np.float32).ravel()[:3])
+        starts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ends = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ctx.sample_rays(ridx, P_inv, center, starts, ends)
+        belief = self.belief.to(dev)
+        out = torch.empty((5, n), dtype=torch.float32, device=dev)
+        ctx.volume_render(starts, ends, center, belief, out)
+        planes = out.cpu().numpy()
+        # ray index = x * H + y: the depth maps' own orientation (forward_pass)
+        return VolumeRender(*[np.ascontiguousarray(p.reshape(W, H).T) for p in planes])
+
+    def render_scene(self, scene, frame_idxs, M=None):
+        """One VolumeRender per frame of `frame_idxs`, from the scene's own cameras."""
+        for i in frame_idxs:
+            yield self.render(scene.get_image(i).camera, scene.image_shape, M)
