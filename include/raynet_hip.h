@@ -844,6 +844,60 @@ int rn_volume_render(rn_ctx *ctx, int32_t n, const float *ray_start, const float
                      const float *camera_center, const float *belief, float *out,
                      int64_t out_stride, void *stream);
 
+/* ---- the surface of a belief grid: an indexed triangle mesh ----
+ *
+ * Marching tetrahedra over the Kuhn split of every lattice cell.  belief [gx][gy][gz] f32, finite;
+ * iso f32; closed 0 / 1; the context's axis tables (rn_set_voxel_grid, else RN_ERR_STATE).
+ *
+ * Lattice: the points (i, j, k), i in [-c, gx - 1 + c] with c = closed, likewise j and k: n = g + 2c
+ * per axis, x slowest and z fastest in the linear order, value 0 outside the grid.  Its cells are
+ * the cubes at the base points (all three coordinates below n - 1), in the base points' order.  A
+ * lattice with an axis of a single point has no cells and its mesh is empty, vertices included.
+ * Coordinates: on axis a the table entry A[i] inside the grid, A[-1] = fl(A[0] - h) and
+ * A[g] = fl(A[g - 1] + h) with h = fl(fl(bbox[3 + a] - bbox[a]) / g).
+ * inside(p) = value(p) >= iso (the side volume.OccupancyVolume.pointcloud takes; NaN is outside).
+ * Edges: (p, d), d in 1..7 (bit 0: +x, bit 1: +y, bit 2: +z) with q = p + d in the lattice; an
+ * edge carries a vertex iff inside(p) != inside(q).  Vertices are ordered by p, then by d.  With
+ * a = value(p), b = value(q), in fp32, every operation rounded on its own, the division IEEE:
+ *     t = (iso - a) / (b - a)
+ *     coordinate = A[p]                             on an axis d does not move along
+ *                  A[p] + t * (A[q] - A[p])         on the others -- always from p to q
+ * Tetrahedra of a cell, as corner masks relative to its base point, in this order:
+ *     [0,1,3,7] [0,1,5,7] [0,2,3,7] [0,2,6,7] [0,4,5,7] [0,4,6,7]
+ * with local corners 0..3 in that order.  Triangles of a tetrahedron, as the edges their corners
+ * lie on:
+ *     one inside corner a, outside o1 < o2 < o3:      (a o1, a o2, a o3)
+ *     three inside i1 < i2 < i3, outside o:           (i1 o, i2 o, i3 o)
+ *     two inside a < b, outside c < d:                (ac, ad, bd) then (ac, bd, bc)
+ * and the last two entries swapped where the right-hand normal would else point from outside to
+ * inside (a constant per tetrahedron and case).  Triangles are ordered by cell, then tetrahedron,
+ * then as above; an entry is the index of the vertex on its edge (base point of the lower mask,
+ * higher mask XOR lower mask).  With closed = 1 the surface is a closed, consistently oriented
+ * 2-manifold for every input (triangles at values equal to iso may have no area); with closed = 0
+ * it is open where it meets the lattice's hull.  The arrays are the same whatever the launch
+ * geometry.
+ *
+ * rn_isosurface_workspace_bytes: the bytes both entries need at `workspace` (8-byte aligned), -1
+ * for a bad argument or a lattice of L points with 12 L >= 2^31.
+ * rn_isosurface_count: classifies every point, scans the counts over the whole lattice and
+ * returns totals_host[0] = nv, totals_host[1] = nf ON THE HOST: it synchronises `stream` and so
+ * cannot be captured into a graph.  A lattice without cells: both 0, no launch.
+ * rn_isosurface_emit: after a count of the same belief, iso, closed and workspace, with its
+ * totals: writes vertices_out [nv][3] f32 and faces_out [nf][3] i32, exactly nv and nf rows (rows
+ * at or beyond nv / nf are never written, whatever the workspace holds).  nv == nf == 0: RN_OK, no
+ * launch.
+ * RN_ERR_INVALID, rn_last_error naming the entry, no launch: a NULL pointer, closed not 0 / 1, a
+ * non-finite iso, iso <= 0 with closed (the padding's 0 must be outside), 12 L >= 2^31, a
+ * workspace that is not 8-byte aligned, nv / nf negative or beyond 7 L / 12 cells.
+ * A non-finite belief may give non-finite positions; it never causes a write out of range: the
+ * counts and every index depend on the comparisons value >= iso only. */
+int64_t rn_isosurface_workspace_bytes(rn_ctx *ctx, int32_t closed);
+int rn_isosurface_count(rn_ctx *ctx, const float *belief, float iso, int32_t closed,
+                        void *workspace, int64_t *totals_host, void *stream);
+int rn_isosurface_emit(rn_ctx *ctx, const float *belief, float iso, int32_t closed,
+                       const void *workspace, int64_t nv, int64_t nf, float *vertices_out,
+                       int32_t *faces_out, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -43,7 +43,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_mesh.inl"), os.path.join(CSRC, "raynet_filters.inl"),
             os.path.join(CSRC, "raynet_cloud.inl"), os.path.join(CSRC, "raynet_batch.inl"),
             os.path.join(CSRC, "raynet_volume.inl"), os.path.join(CSRC, "raynet_volume_args.h"),
-            HEADER]
+            os.path.join(CSRC, "raynet_isosurface.inl"),
+            os.path.join(CSRC, "raynet_isosurface_args.h"), HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
         # RAYNET_HIP_LIB names ANOTHER build of the library (a variant somebody made on purpose):
@@ -205,6 +206,9 @@ SIGNATURES = {
                              _P, _P, _P, _P, _P],
     "rn_occupancy_grid": [_P, _P, _I, _F, _P, _P],
     "rn_volume_render": [_P, _I, _P, _P, _P, _P, _P, _L, _P],
+    "rn_isosurface_workspace_bytes": [_P, _I],
+    "rn_isosurface_count": [_P, _P, _F, _I, _P, _P, _P],
+    "rn_isosurface_emit": [_P, _P, _F, _I, _P, _L, _L, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],
@@ -240,5 +244,6 @@ def load():
     lib.rn_version.restype = ctypes.c_char_p
     lib.rn_acc_size.restype = ctypes.c_int64
     lib.rn_slab_boxes_size.restype = ctypes.c_int64
+    lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib

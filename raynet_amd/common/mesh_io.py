@@ -170,10 +170,11 @@ def parse_gt_data_from_ply(path):
         lists = [p for p in data["face"].values() if p.ndim == 2]
         if len(lists) != 1:
             raise MeshFormatError("%s: the face element needs exactly one list property" % path)
-        if lists[0].shape[1] != 3:
+        if len(lists[0]) and lists[0].shape[1] != 3:      # (`element face 0`: lists of no length)
             raise MeshFormatError("%s: faces have %d vertices; only triangles are supported"
                                   % (path, lists[0].shape[1]))
-        faces = lists[0].astype(np.int64)
+        if len(lists[0]):
+            faces = lists[0].astype(np.int64)
     return points, normals, _check_faces(faces, len(points), path)
 
 

@@ -315,6 +315,29 @@ class HipContext(object):
                                               _stream()))
         return out
 
+    def isosurface(self, belief, iso, closed=True):
+        """rn_isosurface_count / rn_isosurface_emit: the iso-surface of belief [gx][gy][gz] f32 at
+        `iso` by marching tetrahedra -> (vertices (nv, 3) f32, faces (nf, 3) int32), device
+        tensors in the definition's order (include/raynet_hip.h).  closed: the grid is padded
+        with one layer of zeros, so the surface is closed.  Synchronises the stream once (the
+        totals come back to the host to size the outputs)."""
+        _chk(belief, torch.float32, self.G, "belief")
+        closed = 1 if closed else 0
+        size = int(self.lib.rn_isosurface_workspace_bytes(self._h, closed))
+        if size < 0:
+            raise ValueError("isosurface: the lattice of a %s grid is too large" % (self.grid_shape,))
+        work = torch.empty((size,), dtype=torch.uint8, device=belief.device)
+        totals = (ctypes.c_int64 * 2)()
+        self._check(self.lib.rn_isosurface_count(self._h, _ptr(belief), float(iso), closed,
+                                                 _ptr(work), totals, _stream()))
+        nv, nf = int(totals[0]), int(totals[1])
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=belief.device)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=belief.device)
+        self._check(self.lib.rn_isosurface_emit(self._h, _ptr(belief), float(iso), closed,
+                                                _ptr(work), nv, nf, _ptr(vertices), _ptr(faces),
+                                                _stream()))
+        return vertices, faces
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

@@ -16,6 +16,12 @@ frame's camera (volume.OccupancyVolume.render) and OUT_DIR gets
 --ply PATH writes the centres of the voxels whose occupancy is at least --threshold as a point
 cloud: the surface voxels (those with a free or missing 6-neighbour), or with --all_voxels every
 one of them.
+
+--mesh PATH writes the surface of the volume at --threshold as a triangle mesh (a binary PLY;
+volume.OccupancyVolume.mesh: marching tetrahedra, interpolated between the voxel centres), closed
+where the occupied region meets the border of the grid unless --open is given.  --mesh_cloud PATH
+--mesh_samples N [--seed S] writes N area-weighted points of that surface as a point cloud, the
+form compute_metrics scores.
 """
 import argparse
 import os
@@ -42,6 +48,15 @@ def build_parser():
                    help="--ply: a voxel is occupied when its probability is at least this")
     p.add_argument("--all_voxels", action="store_true",
                    help="--ply: every occupied voxel, not only those on the surface")
+    p.add_argument("--mesh", default=None,
+                   help="Also write the surface at --threshold as a triangle mesh (PLY) here")
+    p.add_argument("--open", action="store_true",
+                   help="--mesh / --mesh_cloud: leave the surface open at the border of the grid")
+    p.add_argument("--mesh_cloud", default=None,
+                   help="Also write --mesh_samples points of the surface as a point cloud (PLY) here")
+    p.add_argument("--mesh_samples", type=int, default=None,
+                   help="--mesh_cloud: how many area-weighted points to draw")
+    p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -60,6 +75,12 @@ def main(argv=None):
         args.start_end = _ints(args.start_end)
     if len(args.start_end) != 2:
         parser.error("--start_end takes two numbers, START,END")
+    if args.mesh_cloud and args.mesh_samples is None:
+        parser.error("--mesh_cloud needs --mesh_samples N")
+    if args.mesh_samples is not None and (not args.mesh_cloud or args.mesh_samples < 1):
+        parser.error("--mesh_samples takes a positive number and goes with --mesh_cloud PATH")
+    if (args.mesh or args.mesh_cloud) and not 0.0 < args.threshold <= 1.0:
+        parser.error("--mesh / --mesh_cloud: --threshold must lie in (0, 1]")
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -83,6 +104,15 @@ def main(argv=None):
         np.save(os.path.join(args.output_directory, "opacity_%03d.npy" % (i,)), r.opacity)
     if args.ply:
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
+    if args.mesh or args.mesh_cloud:
+        mesh = volume.mesh(args.threshold, closed=not args.open)
+        if args.mesh:
+            mesh.save_ply(args.mesh)
+        if args.mesh_cloud:
+            if mesh.empty:
+                parser.error("no voxel reaches --threshold %g: the surface is empty and has no "
+                             "points to sample" % args.threshold)
+            mesh.pointcloud(args.mesh_samples, args.seed).save_ply(args.mesh_cloud)
     return 0
 
 

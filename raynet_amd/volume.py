@@ -5,7 +5,13 @@ point cloud of its occupied voxels and rendered from any camera -- a reference i
 a held-out view, a camera that has no image at all.  The belief grid and
 the rendering are HIP kernels (csrc/raynet_volume.inl, rn_occupancy_grid / rn_volume_render); the
 voxel cloud is one pass of torch operations over the grid.
+
+`OccupancyVolume.mesh()` is the surface of the volume: the iso-surface of the belief grid as an
+indexed, closed, consistently oriented triangle mesh (`SurfaceMesh`; marching tetrahedra on the
+GPU, csrc/raynet_isosurface.inl), which the mesh tools of the package take:
+`MeshRaycaster`, its `sample_surface`, and through the sampled cloud the metrics.
 """
+
 import numpy as np
 import torch
 
@@ -34,6 +40,71 @@ class VolumeRender(object):
 
     def __iter__(self):
         return iter(tuple(getattr(self, f) for f in self.FIELDS))
+
+
+class SurfaceMesh(object):
+    """An indexed triangle mesh: vertices (n, 3) float32, faces (m, 3) int32 rows of vertex
+    indices, counter-clockwise seen from outside (host arrays; tensors are copied to the host)."""
+
+    def __init__(self, vertices, faces):
+        if isinstance(vertices, torch.Tensor):
+            vertices = vertices.detach().cpu().numpy()
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        faces = np.asarray(faces).reshape(-1, 3)
+        if len(faces) and (faces.min() < 0 or faces.max() >= len(self.vertices)):
+            raise ValueError("faces: a vertex index outside 0..%d" % (len(self.vertices) - 1))
+        self.faces = np.ascontiguousarray(faces, dtype=np.int32)
+
+    @property
+    def empty(self):
+        return len(self.faces) == 0
+
+    def triangles(self):
+        """[m, 9] float32 rows p0 | p1 | p2: what `MeshRaycaster` takes."""
+        from .common.mesh_io import get_triangles
+        return get_triangles(self.vertices, self.faces)
+
+    # ---- file ------------------------------------------------------------------------------
+    def save_ply(self, path):
+        """A binary little-endian PLY: `vertex` x y z float, `face` one list vertex_indices of
+        uchar 3 and three ints -- the file common.mesh_io.parse_gt_data_from_ply reads back to
+        the same arrays."""
+        rows = np.empty((len(self.faces),), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        rows["n"] = 3
+        rows["v"] = self.faces
+        with open(path, "wb") as f:
+            f.write(("ply\nformat binary_little_endian 1.0\ncomment raynet_amd surface mesh\n"
+                     "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                     "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                     % (len(self.vertices), len(self.faces))).encode())
+            self.vertices.astype("<f4").tofile(f)
+            rows.tofile(f)
+
+    @classmethod
+    def load_ply(cls, path):
+        from .common.mesh_io import parse_gt_data_from_ply
+        points, _, faces = parse_gt_data_from_ply(path)
+        return cls(points, faces)
+
+    # ---- the mesh tools --------------------------------------------------------------------
+    def raycaster(self):
+        """-> raynet_amd.mesh.MeshRaycaster over the triangles (ray casting, closest points,
+        area, sample_surface)."""
+        if self.empty:
+            raise ValueError("the mesh is empty: there is no surface to cast rays at or to sample")
+        from .mesh import MeshRaycaster
+        return MeshRaycaster(self.triangles())
+
+    def pointcloud(self, n_samples, seed=0):
+        """-> raynet_amd.pointcloud.Pointcloud of `n_samples` area-weighted points of the
+        surface (MeshRaycaster.sample_surface), for the point-cloud filters and the metrics."""
+        if self.empty:
+            raise ValueError("the mesh is empty: there is no surface to cast rays at or to sample")
+        from .pointcloud import Pointcloud
+        points, _ = self.raycaster().sample_surface(n_samples, seed)
+        return Pointcloud(np.ascontiguousarray(points.cpu().numpy().T))
 
 
 class OccupancyVolume(object):
@@ -88,6 +159,22 @@ class OccupancyVolume(object):
             keep = occ & ~inner
         centres = get_voxel_grid(self.bbox, self.grid_shape).reshape(3, -1)
         return Pointcloud(np.ascontiguousarray(centres[:, keep.reshape(-1).cpu().numpy()]))
+
+    # ---- the surface ------------------------------------------------------------------------
+    def mesh(self, threshold=0.5, closed=True):
+        """-> SurfaceMesh: the surface belief = threshold, interpolated between the voxel centres
+        (marching tetrahedra, HipContext.isosurface); the side belief >= threshold is inside, as
+        for `pointcloud`.  closed: the grid counts as surrounded by free space, so the surface is
+        closed also where the occupied region meets the border of the grid; else it is open
+        there."""
+        threshold = float(threshold)
+        if not 0.0 < threshold <= 1.0:
+            raise ValueError("threshold: a probability in (0, 1], got %r" % (threshold,))
+        if not bool(torch.isfinite(self.belief).all()):
+            raise ValueError("the belief has non-finite values: no surface is defined")
+        ctx = self._context((1, 1), None)
+        vertices, faces = ctx.isosurface(self.belief.to(ctx.device), threshold, closed)
+        return SurfaceMesh(vertices, faces)
 
     # ---- rendering -------------------------------------------------------------------------
     def _context(self, image_shape, M):

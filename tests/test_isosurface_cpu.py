@@ -1,0 +1,181 @@
+"""The iso-surface's host side (no GPU): the three entries in the header and the ctypes table,
+SurfaceMesh's file, render_volume's flags, and the size arithmetic and argument checks of the
+launchers (raynet_amd/csrc/raynet_isosurface_args.h) as a stand-alone program under the address
+and undefined-behaviour sanitizers -- nothing sanitised is loaded into this interpreter."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import isosurface_truth as it
+from conftest import REPO
+
+F = np.float32
+
+
+def _prototype(name):
+    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
+    assert m is not None, "%s is not declared in include/raynet_hip.h" % name
+    return m.group(1), [" ".join(a.split()) for a in m.group(2).split(",")]
+
+
+@pytest.mark.parametrize("name,returns,params", [
+    ("rn_isosurface_workspace_bytes", "int64_t", ["rn_ctx *ctx", "int32_t closed"]),
+    ("rn_isosurface_count", "int",
+     ["rn_ctx *ctx", "const float *belief", "float iso", "int32_t closed", "void *workspace",
+      "int64_t *totals_host", "void *stream"]),
+    ("rn_isosurface_emit", "int",
+     ["rn_ctx *ctx", "const float *belief", "float iso", "int32_t closed",
+      "const void *workspace", "int64_t nv", "int64_t nf", "float *vertices_out",
+      "int32_t *faces_out", "void *stream"]),
+])
+def test_entries_are_declared_and_bound_with_matching_arity(name, returns, params):
+    from raynet_amd import _lib
+    declared_returns, declared = _prototype(name)
+    assert declared_returns == returns and declared == params
+    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(declared)
+    # scalars where the header has scalars, pointers elsewhere
+    for arg, ctype in zip(declared, _lib.SIGNATURES[name]):
+        want = (ctypes.c_void_p if "*" in arg else
+                ctypes.c_int32 if arg.startswith("int32_t") else
+                ctypes.c_int64 if arg.startswith("int64_t") else
+                ctypes.c_float if arg.startswith("float ") else None)
+        assert ctype is want, (name, arg, ctype)
+    path = _lib.build()
+    assert hasattr(ctypes.CDLL(path), name)
+
+
+def test_the_kernel_file_is_plain_hip_and_listed():
+    from raynet_amd import _lib
+    csrc = os.path.join(REPO, "raynet_amd", "csrc")
+    src = open(os.path.join(csrc, "raynet_isosurface.inl")).read()
+    assert "asm" not in re.sub(r"//.*", "", src)
+    for f in ("raynet_isosurface.inl", "raynet_isosurface_args.h"):
+        assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", open(os.path.join(csrc, f)).read(),
+                             re.M), f
+    assert open(os.path.join(csrc, "raynet_hip.hip")).read().rstrip().endswith(
+        '#include "raynet_isosurface.inl"')
+    # the launchers decide on the header's verdicts and the kernel guards its rows with row_in
+    assert "rn_iso::count_args(" in src and "rn_iso::emit_args(" in src
+    assert src.count("rn_iso::row_in(") == 2 and src.count("rn_iso::row_index(") == 4
+    # a change of either file rebuilds the library
+    import inspect
+    build = inspect.getsource(_lib.build)
+    assert '"raynet_isosurface.inl"' in build and '"raynet_isosurface_args.h"' in build
+
+
+def test_the_table_in_the_kernel_file_is_the_derived_one():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "isosurface_table.py"),
+                        "--check"],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+
+
+def test_launcher_arithmetic_under_sanitizers(tmp_path):
+    exe = str(tmp_path / "isosurface_args")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
+                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(REPO, "raynet_amd", "csrc"),
+                           os.path.join(REPO, "tests", "isosurface_args_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    assert r.stdout.strip().endswith("isosurface_args: ok"), r.stdout
+
+
+# ------------------------------------------------------------------------- SurfaceMesh
+def _ball_mesh():
+    from raynet_amd.volume import SurfaceMesh
+    belief = it.logistic_ball()
+    bbox, axes = it.unit_frame(belief.shape)
+    return SurfaceMesh(*it.extract(belief, 0.5, True, axes, bbox))
+
+
+def test_surface_mesh_ply_round_trip_through_mesh_io(tmp_path):
+    from raynet_amd.common.mesh_io import get_triangles, parse_gt_data_from_ply
+    from raynet_amd.volume import SurfaceMesh
+    mesh = _ball_mesh()
+    assert mesh.vertices.dtype == F and mesh.faces.dtype == np.int32 and not mesh.empty
+    path = str(tmp_path / "ball.ply")
+    mesh.save_ply(path)
+    head = open(path, "rb").read(400).split(b"end_header\n")[0].decode().split("\n")
+    assert head[:2] == ["ply", "format binary_little_endian 1.0"]
+    assert [l for l in head if l.startswith(("element", "property"))] == [
+        "element vertex 756", "property float x", "property float y", "property float z",
+        "element face 1508", "property list uchar int vertex_indices"]
+    points, normals, faces = parse_gt_data_from_ply(path)
+    assert points.dtype == F and np.array_equal(points.view(np.int32), mesh.vertices.view(np.int32))
+    assert normals.shape == (756, 0)
+    assert faces.shape == (1508, 3) and np.array_equal(faces, mesh.faces)
+    again = SurfaceMesh.load_ply(path)
+    assert again.faces.dtype == np.int32 and np.array_equal(again.faces, mesh.faces)
+    assert np.array_equal(again.vertices.view(np.int32), mesh.vertices.view(np.int32))
+    tri = mesh.triangles()
+    assert tri.shape == (1508, 9) and tri.dtype == F
+    assert np.array_equal(tri, get_triangles(points, faces))
+    assert np.array_equal(tri[5], mesh.vertices[mesh.faces[5]].reshape(9))
+    with pytest.raises(ValueError):
+        SurfaceMesh(mesh.vertices, mesh.faces + 1)
+
+
+def test_empty_surface_mesh(tmp_path):
+    from raynet_amd.common.mesh_io import parse_gt_data_from_ply
+    from raynet_amd.volume import SurfaceMesh
+    mesh = SurfaceMesh(np.zeros((0, 3), F), np.zeros((0, 3), np.int32))
+    assert mesh.empty and mesh.triangles().shape == (0, 9)
+    path = str(tmp_path / "empty.ply")
+    mesh.save_ply(path)
+    points, _, faces = parse_gt_data_from_ply(path)
+    assert points.shape == (0, 3) and faces.shape == (0, 3)
+    again = SurfaceMesh.load_ply(path)
+    assert again.empty and again.vertices.shape == (0, 3) and again.faces.dtype == np.int32
+    with pytest.raises(ValueError, match="the mesh is empty"):
+        mesh.raycaster()
+    with pytest.raises(ValueError, match="the mesh is empty"):
+        mesh.pointcloud(10)
+
+
+def test_mesh_refuses_thresholds_and_beliefs_without_a_surface():
+    from raynet_amd.volume import OccupancyVolume
+    belief = it.logistic_ball()
+    volume = OccupancyVolume(belief, (0, 0, 0, 1, 1, 1), belief.shape)
+    for threshold in (0.0, -0.5, 1.5, float("nan")):
+        with pytest.raises(ValueError, match="threshold"):
+            volume.mesh(threshold)
+    for bad in (np.nan, np.inf):
+        holed = belief.copy()
+        holed[3, 4, 5] = bad
+        with pytest.raises(ValueError, match="non-finite"):
+            OccupancyVolume(holed, (0, 0, 0, 1, 1, 1), belief.shape).mesh()
+
+
+# ------------------------------------------------------------------------ render_volume
+def test_render_volume_parser_knows_the_mesh_flags(tmp_path, capsys):
+    from raynet_amd.scripts import render_volume
+    p = render_volume.build_parser()
+    a = p.parse_args(["scene", "occupancy.npz", "out"])
+    assert (a.mesh, a.open, a.mesh_cloud, a.mesh_samples, a.seed) == (None, False, None, None, 0)
+    # what was there is as it was
+    assert a.plane == "depth" and a.ply is None and a.threshold == 0.5 and a.all_voxels is False
+    a = p.parse_args(["s", "o.npz", "out", "--mesh", "m.ply", "--threshold", "0.4", "--open",
+                      "--mesh_cloud", "c.ply", "--mesh_samples", "5000", "--seed", "7"])
+    assert (a.mesh, a.threshold, a.open, a.mesh_cloud, a.mesh_samples, a.seed) == \
+        ("m.ply", 0.4, True, "c.ply", 5000, 7)
+    occupancy = str(tmp_path / "occupancy.npz")
+    open(occupancy, "wb").close()
+    for argv, message in [
+            (["--mesh_cloud", "c.ply"], "--mesh_cloud needs --mesh_samples"),
+            (["--mesh_samples", "100"], "--mesh_samples"),
+            (["--mesh_cloud", "c.ply", "--mesh_samples", "0"], "--mesh_samples"),
+            (["--mesh", "m.ply", "--threshold", "0"], "--threshold"),
+            (["--mesh", "m.ply", "--threshold", "1.5"], "--threshold")]:
+        with pytest.raises(SystemExit) as e:
+            render_volume.main(["scene", occupancy, str(tmp_path / "out")] + argv)
+        assert e.value.code == 2
+        assert message in capsys.readouterr().err
+    assert not os.path.exists(str(tmp_path / "out"))
