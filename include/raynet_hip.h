@@ -898,6 +898,66 @@ int rn_isosurface_emit(rn_ctx *ctx, const float *belief, float iso, int32_t clos
                        const void *workspace, int64_t nv, int64_t nf, float *vertices_out,
                        int32_t *faces_out, void *stream);
 
+/* ---- what a surface looks like: vertex normals and colours from the images ----
+ *
+ * All arrays are device memory.  Every floating-point operation below is fp64 and rounded on its
+ * own, in the order written (the library is built with -ffp-contract=off); only + - * /, floor,
+ * rint, comparisons and conversions occur -- no sqrt -- so a NumPy restatement gives the same bits
+ * (tests/appearance_truth.py).
+ *
+ * rn_vertex_area_normals: vertices [nv][3] f32, faces [nf][3] i32, the corner table of the mesh
+ * by vertex -- corners [3 nf] i32: the indices c = 3 face + slot of the flattened `faces`, sorted
+ * by the vertex they name, ascending c within a vertex; offsets [nv + 1] i32: the exclusive prefix
+ * of the vertices' corner counts -- and normals [nv][3] f32, written.  One thread per vertex v,
+ * over k = offsets[v] .. offsets[v + 1] - 1 in that order:
+ *     f = corners[k] / 3;  p0, p1, p2 = the vertices of faces[f];  e1 = p1 - p0;  e2 = p2 - p0
+ *     a = (e1.y e2.z - e1.z e2.y,  e1.z e2.x - e1.x e2.z,  e1.x e2.y - e1.y e2.x);  s = s + a
+ * and normals[v] = (float) s: area-weighted, NOT normalised (its length is twice the area around
+ * the vertex); (0, 0, 0) for a vertex in no face.  A k outside [0, 3 nf), a corner outside
+ * [0, 3 nf) and a face with a vertex index outside [0, nv) are skipped: whatever the three index
+ * arrays hold, nothing is read or written out of bounds.  nv == 0: RN_OK, no launch.
+ * RN_ERR_INVALID, rn_last_error naming the entry, no launch: nv or nf negative, nv > 2^31 - 2,
+ * 3 nf > 2^31 - 1, a NULL vertices / offsets / normals, a NULL faces / corners with nf > 0.
+ *
+ * rn_project_colors: points [n][3] f32; normals [n][3] f32 or NULL; cameras [V][15] f64, a row
+ * P [3][4] row-major | centre [3]; images [V][H][W][C] f32; depths [V][H][W] f32 or NULL,
+ * distances to the camera centre; pixel centres at whole coordinates (both as rn_depthmap_points
+ * and rn_consistency_tau have them).  1 <= C <= 4, 0 <= V <= 32.  Written: colors [n][C] f32,
+ * weight [n] f32, views [n] u32 -- all n rows, always, also with V == 0.  One thread per point
+ * p = (x, y, z) with normal n, the views v in ascending order:
+ *   projection  h_k = ((P_k0 x + P_k1 y) + P_k2 z) + P_k3;  X = h_0 / h_2;  Y = h_1 / h_2
+ *               d = c - p;  dd = (d_x^2 + d_y^2) + d_z^2
+ *   in view     0 < h_2 < inf,  dd > 0,  border <= X <= (W - 1) - border,
+ *               border <= Y <= (H - 1) - border          (a NaN fails every test)
+ *   facing      with normals and nn = (n_x^2 + n_y^2) + n_z^2 > 0:
+ *                   dot = (n_x d_x + n_y d_y) + n_z d_z;  q = nn dd
+ *                   the view counts only if dot > 0 and dot dot > (min_cos min_cos) q
+ *                   w = (dot dot) / q                     (cos^2)
+ *               else w = 1 and there is no facing test
+ *   occlusion   with depths: z = depths[v][rint(Y)][rint(X)] (half to even);  lim = z + tol
+ *               the view counts only if z > 0 and dd <= lim lim  -- one-sided: a point in front
+ *               of the recorded surface is seen; z = +inf occludes nothing; 0, a negative value
+ *               or NaN hides the point
+ *   colour      x0 = floor(X);  x1 = min(x0 + 1, W - 1);  fx = X - x0;  likewise y
+ *               top = I00 + fx (I01 - I00);  bot = I10 + fx (I11 - I10);  col = top + fy (bot - top)
+ *   combination mode 0 (blend): num_c = num_c + w col_c;  den = den + w;  colors = (float)(num_c / den)
+ *               mode 1 (best):  colors = (float) col of the first view with the largest w
+ *               weight = (float) den in both modes;  bit v of views is set iff view v counted
+ * A point no view counts for has colour 0, weight 0 and views 0.  A view that does not count
+ * reads pixel (0, 0) of its image and depth map, so every load lies inside the arrays whatever the
+ * point.  n == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch: n
+ * negative, n C > 2^31 - 1, V outside 0..32, C outside 1..4, H or W below 1, tol negative or not
+ * finite, min_cos outside [0, 1), border negative or not finite, mode outside {0, 1}, a NULL
+ * points / colors / weight / views, a NULL cameras / images with V > 0. */
+int rn_vertex_area_normals(rn_ctx *ctx, int64_t nv, const float *vertices, int64_t nf,
+                           const int32_t *faces, const int32_t *offsets, const int32_t *corners,
+                           float *normals, void *stream);
+int rn_project_colors(rn_ctx *ctx, int64_t n, const float *points, const float *normals,
+                      int32_t V, const double *cameras, int32_t H, int32_t W, int32_t C,
+                      const float *images, const float *depths, double tol, double min_cos,
+                      double border, int32_t mode, float *colors, float *weight, uint32_t *views,
+                      void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

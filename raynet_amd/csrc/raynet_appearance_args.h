@@ -1,0 +1,75 @@
+// raynet_appearance_args.h -- the argument checks and the index arithmetic of
+// rn_vertex_area_normals / rn_project_colors (raynet_appearance.inl), host-only and free of HIP so
+// that they compile into a stand-alone program (tests/appearance_args_main.cpp, built with the
+// address and undefined-behaviour sanitizers by tests/test_appearance_cpu.py).  The launchers act
+// on the verdicts; the kernels guard and address their reads with the constexpr functions below.
+#pragma once
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+namespace rn_app {
+
+constexpr int MAX_VIEWS = 32;           // one bit of the `views` word each
+constexpr int MAX_CHANNELS = 4;
+constexpr int CAMERA_DOUBLES = 15;      // P [3][4] row-major | centre [3]
+constexpr int64_t INT32_LIMIT = ((int64_t)1 << 31) - 1;
+
+enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
+
+// rn_vertex_area_normals.  The scalars first, then nv == 0 (nothing to write: EMPTY, whatever the
+// pointers), then the pointers: faces and corners are read only where there are faces.
+inline Verdict normals_args(bool have_ctx, int64_t nv, const void *vertices, int64_t nf,
+                            const void *faces, const void *offsets, const void *corners,
+                            const void *normals) {
+    if (!have_ctx || nv < 0 || nf < 0) return INVALID;
+    if (nv > INT32_LIMIT - 1) return INVALID;       // offsets has nv + 1 entries, indices are int32
+    if (nf > INT32_LIMIT / 3) return INVALID;       // a corner 3 f + slot is an int32
+    if (nv == 0) return EMPTY;
+    if (!vertices || !offsets || !normals) return INVALID;
+    if (nf > 0 && (!faces || !corners)) return INVALID;
+    return LAUNCH;
+}
+
+// rn_project_colors, in the same order.  images and cameras are read only where there are views;
+// normals and depths may be null (no facing test / no occlusion test).
+inline Verdict colors_args(bool have_ctx, int64_t n, const void *points, int32_t V,
+                           const void *cameras, int32_t H, int32_t W, int32_t C,
+                           const void *images, double tol, double min_cos, double border,
+                           int32_t mode, const void *colors, const void *weight,
+                           const void *views) {
+    if (!have_ctx || n < 0) return INVALID;
+    if (V < 0 || V > MAX_VIEWS) return INVALID;
+    if (C < 1 || C > MAX_CHANNELS) return INVALID;
+    if (H < 1 || W < 1) return INVALID;
+    if (n > INT32_LIMIT / C) return INVALID;        // an entry n C + c of `colors` is an int32
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return INVALID;
+    if (!(min_cos >= 0.0) || !(min_cos < 1.0)) return INVALID;
+    if (!(border >= 0.0) || !std::isfinite(border)) return INVALID;
+    if (mode != 0 && mode != 1) return INVALID;
+    if (n == 0) return EMPTY;
+    if (!points || !colors || !weight || !views) return INVALID;
+    if (V > 0 && (!cameras || !images)) return INVALID;
+    return LAUNCH;
+}
+
+// ---- what the kernels guard and address with (constexpr: the same functions on the device) ----
+// the corner c = 3 f + slot names an entry of `faces`
+constexpr bool corner_in(int64_t c, int64_t nf) { return c >= 0 && c < 3 * nf; }
+constexpr bool vertex_in(int64_t v, int64_t nv) { return v >= 0 && v < nv; }
+// the range [first, last) of a vertex's corners, cut to the entries `corners` has
+constexpr int64_t clamp_slot(int64_t k, int64_t nf) { return k < 0 ? 0 : (k > 3 * nf ? 3 * nf : k); }
+constexpr size_t xyz_index(int64_t row, int column) { return 3 * (size_t)row + (size_t)column; }
+
+// pixel (view, y, x) of a [V][H][W] map, channel c of a [V][H][W][C] image
+constexpr size_t depth_index(int v, int y, int x, int H, int W) {
+    return ((size_t)v * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
+}
+constexpr size_t image_index(int v, int y, int x, int c, int H, int W, int C) {
+    return depth_index(v, y, x, H, W) * (size_t)C + (size_t)c;
+}
+// a pixel coordinate of a view that counts lies in [0, extent - 1]; everything else reads pixel 0
+constexpr bool pixel_in(int at, int extent) { return at >= 0 && at < extent; }
+
+}  // namespace rn_app

@@ -1234,5 +1234,9 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // the occupancy volume: belief grid of an accumulator, rendered along rays
 #include "raynet_volume.inl"
 
+// what the surface looks like: vertex normals, colours from the scene's images (DESIGN.md
+// section 20)
+#include "raynet_appearance.inl"
+
 // the surface of a belief grid: marching tetrahedra and the grid-level scan
 #include "raynet_isosurface.inl"

@@ -338,6 +338,48 @@ class HipContext(object):
                                                 _stream()))
         return vertices, faces
 
+    # ---- normals and colours (raynet_amd/appearance.py) --------------------------------------
+    def vertex_area_normals(self, vertices, faces, offsets, corners, normals=None):
+        """rn_vertex_area_normals: vertices (nv, 3) f32, faces (nf, 3) i32 and the mesh's corner
+        table by vertex (offsets [nv + 1] i32, corners [3 nf] i32) -> normals (nv, 3) f32, the
+        area-weighted sums of the face normals around every vertex (not normalised)."""
+        nv, nf = len(vertices), len(faces)
+        _chk(vertices, torch.float32, 3 * nv, "vertices")
+        _chk(faces, torch.int32, 3 * nf, "faces")
+        _chk(offsets, torch.int32, nv + 1, "offsets")
+        _chk(corners, torch.int32, 3 * nf, "corners")
+        if normals is None:
+            normals = torch.empty((nv, 3), dtype=torch.float32, device=vertices.device)
+        _chk(normals, torch.float32, 3 * nv, "normals")
+        self._check(self.lib.rn_vertex_area_normals(self._h, nv, _ptr(vertices), nf, _ptr(faces),
+                                                    _ptr(offsets), _ptr(corners), _ptr(normals),
+                                                    _stream()))
+        return normals
+
+    def project_colors(self, points, normals, cameras, images, depths, tol, min_cos, border, mode,
+                       colors, weight, views):
+        """rn_project_colors: points (n, 3) f32, normals (n, 3) f32 or None, cameras (V, 15) f64,
+        images (V, H, W, C) f32, depths (V, H, W) f32 or None -> colors (>= n, C) f32, weight
+        [>= n] f32, views [>= n] int32 (the bits of the u32 mask); mode 0: blend, 1: best."""
+        n, V = len(points), len(cameras)
+        if images.dim() != 4 or images.shape[0] != V:
+            raise ValueError("images: expected (%d, H, W, C), got %s" % (V, tuple(images.shape)))
+        H, W, C = (int(s) for s in images.shape[1:])
+        _chk(points, torch.float32, 3 * n, "points")
+        _chk(normals, torch.float32, 3 * n, "normals", optional=True)
+        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
+        _chk(images, torch.float32, V * H * W * C, "images")
+        _chk(depths, torch.float32, V * H * W, "depths", optional=True)
+        _chk(colors, torch.float32, n * C, "colors")
+        _chk(weight, torch.float32, n, "weight")
+        _chk(views, torch.int32, n, "views")
+        if cameras.dim() != 2 or cameras.shape[1] != 15:
+            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
+        self._check(self.lib.rn_project_colors(
+            self._h, n, _ptr(points), _ptr(normals), V, _ptr(cameras), H, W, C, _ptr(images),
+            _ptr(depths), float(tol), float(min_cos), float(border), int(mode), _ptr(colors),
+            _ptr(weight), _ptr(views), _stream()))
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

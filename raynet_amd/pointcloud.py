@@ -64,6 +64,41 @@ class Pointcloud(object):
                      "end_header\n" % (sys.byteorder, N)).encode())
             vertices.tofile(f)
 
+    def save_rgb_ply(self, file, colors):
+        """xyz float32 then uchar RGB per vertex, the header layout of `save_colored_ply`;
+        colors: (N, 3) uint8, e.g. what `colorize` returns."""
+        N = self.points.shape[1]
+        colors = np.asarray(colors)
+        if colors.shape != (N, 3) or colors.dtype != np.uint8:
+            raise ValueError("colors: expected uint8 of shape (%d, 3), got %s of shape %s"
+                             % (N, colors.dtype, colors.shape))
+        vertices = np.empty((N,), dtype=[("xyz", np.float32, 3), ("rgb", np.uint8, 3)])
+        vertices["xyz"] = np.asarray(self.points).T
+        vertices["rgb"] = colors
+        with open(file, "wb") as f:
+            f.write(("ply\nformat binary_%s_endian 1.0\ncomment Raynet pointcloud!\n"
+                     "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                     "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                     "end_header\n" % (sys.byteorder, N)).encode())
+            vertices.tofile(f)
+
+    def colorize(self, scene, frame_idxs, depthmaps, tol, border=0, mode="blend",
+                 unseen=(0.5, 0.5, 0.5)):
+        """Colours of the points from the images of the scene's frames `frame_idxs` -> (colors
+        (N, 3) uint8, views [N] uint32, bit k: frame_idxs[k] saw the point).  depthmaps: one per
+        frame (.npy file names or arrays), the occluders: a frame sees a point that projects at
+        least `border` pixels inside its image and is no farther from its camera than the map's
+        value there plus `tol` (scene units).  There are no normals: every frame that sees a point
+        weighs the same.  A point no frame sees gets `unseen`.  (appearance.project_colors)"""
+        from .appearance import project_colors, scene_views, to_rgb8
+        cameras, images = scene_views(scene, frame_idxs)
+        if len(depthmaps) != len(cameras):
+            raise ValueError("%d depth maps for %d frames" % (len(depthmaps), len(cameras)))
+        maps = [np.load(d) if isinstance(d, str) else d for d in depthmaps]
+        got = project_colors(np.ascontiguousarray(np.asarray(self.points).T, dtype=np.float32),
+                             cameras, images, maps, None, tol=tol, border=border, mode=mode)
+        return to_rgb8(got.colors, got.seen, unseen), got.views
+
     def save(self, file):
         np.save(file, self.points)
 

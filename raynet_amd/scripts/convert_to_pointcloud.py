@@ -11,7 +11,11 @@ d; -1, the default, is off) -- the filtered cloud is saved as filtered_predicted
 as well, and each filter leaves its own PLY in OUTPUT_DIR.  The flags are the reference's, with
 its defaults; --seed is new: the thinning's visiting order (the reference shuffles unseeded),
 and so is --min_confidence X: pixels whose confidence (PREDICTIONS_DIR/confidence_%03d.npy, what
-`forward_pass --depth_statistics` writes) is below X do not become points.
+`forward_pass --depth_statistics` writes) is below X do not become points.  --color is new too: the
+clouds are also saved with the colours of the chosen frames' images, as colored_predicted_pc_s_%d.ply
+(and colored_filtered_predicted_pc_s_%d.ply when filters ran): a frame colours the points it sees,
+with the predicted depth maps as occluders at the tolerance --consistency_threshold, and the frames
+that see a point are blended (Pointcloud.colorize).  At most 32 frames.
 """
 import argparse
 import os
@@ -74,14 +78,21 @@ def build_parser():
     p.add_argument("--min_confidence", default=None, type=float,
                    help="Drop the pixels whose confidence (confidence_%%03d.npy in the predictions "
                         "directory, from forward_pass --depth_statistics) is below this (default: off)")
+    p.add_argument("--color", action="store_true",
+                   help="Also write the clouds with the colours of the chosen frames' images "
+                        "(colored_*.ply; the depth maps occlude, at --consistency_threshold)")
     return p
 
 
 def main(argv=None):
     """-> (predicted cloud, filtered cloud or None), after writing the PLY files."""
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     if isinstance(args.frame_idxs, str):
         args.frame_idxs = frame_idxs_type(args.frame_idxs)
+    if args.color and not args.consistency_threshold >= 0:
+        parser.error("--color: --consistency_threshold is the occlusion tolerance and cannot be "
+                     "negative")
     from raynet_amd.common.scene import get_scene
     if args.dataset_type == "dtu":
         scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
@@ -119,12 +130,22 @@ def run(scene, args):
     print("Saving predicted point-cloud for scene %d ..." % (args.scene_idx,))
     predicted_pointcloud.save_ply(
         os.path.join(args.output_directory, "predicted_pc_s_%d.ply" % (args.scene_idx,)))
+
+    def save_colored(name):
+        if getattr(args, "color", False):
+            colors, _ = predicted_pointcloud.colorize(scene, frame_idxs, depthmaps,
+                                                      tol=args.consistency_threshold)
+            predicted_pointcloud.save_rgb_ply(
+                os.path.join(args.output_directory, name % (args.scene_idx,)), colors)
+
+    save_colored("colored_predicted_pc_s_%d.ply")
     unfiltered = predicted_pointcloud.points
     if not filter_factory.has_filters:
         return unfiltered, None
     predicted_pointcloud.filter(filter_factory)
     predicted_pointcloud.save_ply(
         os.path.join(args.output_directory, "filtered_predicted_pc_s_%d.ply" % (args.scene_idx,)))
+    save_colored("colored_filtered_predicted_pc_s_%d.ply")
     return unfiltered, predicted_pointcloud.points
 
 

@@ -22,6 +22,14 @@ volume.OccupancyVolume.mesh: marching tetrahedra, interpolated between the voxel
 where the occupied region meets the border of the grid unless --open is given.  --mesh_cloud PATH
 --mesh_samples N [--seed S] writes N area-weighted points of that surface as a point cloud, the
 form compute_metrics scores.
+
+--color, with --mesh: the mesh file also carries vertex normals and the colours of the images of
+the frames of --start_end / --skip_every (at most 32; volume.SurfaceMesh.colorize).  A frame
+colours the vertices that face it and that the mesh itself does not hide from it; --color_mode
+blend (default) takes the cos^2-weighted mean of the frames, best the frame that faces a vertex
+best.  --depth_tolerance is the slack of the occlusion test in voxel diagonals (default 1: a
+vertex lies on an edge of a lattice cell, and the surface point its nearest pixel records lies in
+the same or the next cell unless the view is grazing).
 """
 import argparse
 import os
@@ -57,6 +65,12 @@ def build_parser():
     p.add_argument("--mesh_samples", type=int, default=None,
                    help="--mesh_cloud: how many area-weighted points to draw")
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
+    p.add_argument("--color", action="store_true",
+                   help="--mesh: with vertex normals and the colours of the frames' images")
+    p.add_argument("--color_mode", choices=["blend", "best"], default="blend",
+                   help="--color: the weighted mean of the frames that see a vertex, or the best one")
+    p.add_argument("--depth_tolerance", type=float, default=1.0,
+                   help="--color: the slack of the occlusion test, in voxel diagonals")
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -81,6 +95,10 @@ def main(argv=None):
         parser.error("--mesh_samples takes a positive number and goes with --mesh_cloud PATH")
     if (args.mesh or args.mesh_cloud) and not 0.0 < args.threshold <= 1.0:
         parser.error("--mesh / --mesh_cloud: --threshold must lie in (0, 1]")
+    if args.color and not args.mesh:
+        parser.error("--color goes with --mesh PATH: the colours are the mesh's")
+    if not (args.depth_tolerance >= 0.0 and args.depth_tolerance < float("inf")):
+        parser.error("--depth_tolerance takes a finite number of voxel diagonals, 0 or more")
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -98,6 +116,9 @@ def main(argv=None):
     os.makedirs(args.output_directory, exist_ok=True)
     start, end = args.start_end
     frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
+    if args.color and len(frames) > 32:
+        parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
+                     "--skip_every" % len(frames))
     for i, r in zip(frames, volume.render_scene(scene, frames)):
         np.save(os.path.join(args.output_directory, "depth_%03d.npy" % (i,)),
                 getattr(r, args.plane))
@@ -106,6 +127,15 @@ def main(argv=None):
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
     if args.mesh or args.mesh_cloud:
         mesh = volume.mesh(args.threshold, closed=not args.open)
+        if args.mesh and args.color:
+            if mesh.empty or not frames:
+                parser.error("--color: %s" % ("the surface is empty" if mesh.empty else
+                                              "--start_end selects no frame of the scene"))
+            bbox = volume.bbox.astype(np.float64)
+            voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
+            mesh.compute_normals()
+            mesh.colorize(scene, frames, tol=args.depth_tolerance * float(np.sqrt((voxel ** 2).sum())),
+                          mode=args.color_mode)
         if args.mesh:
             mesh.save_ply(args.mesh)
         if args.mesh_cloud:

@@ -44,9 +44,11 @@ class VolumeRender(object):
 
 class SurfaceMesh(object):
     """An indexed triangle mesh: vertices (n, 3) float32, faces (m, 3) int32 rows of vertex
-    indices, counter-clockwise seen from outside (host arrays; tensors are copied to the host)."""
+    indices, counter-clockwise seen from outside (host arrays; tensors are copied to the host).
+    Optional per-vertex attributes: normals (n, 3) float32 (`compute_normals`) and colors (n, 3)
+    uint8 (`colorize`); both go into the file when set."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, normals=None, colors=None):
         if isinstance(vertices, torch.Tensor):
             vertices = vertices.detach().cpu().numpy()
         if isinstance(faces, torch.Tensor):
@@ -56,6 +58,18 @@ class SurfaceMesh(object):
         if len(faces) and (faces.min() < 0 or faces.max() >= len(self.vertices)):
             raise ValueError("faces: a vertex index outside 0..%d" % (len(self.vertices) - 1))
         self.faces = np.ascontiguousarray(faces, dtype=np.int32)
+        self.normals = self.colors = None
+        if normals is not None:
+            self.normals = self._attribute(normals, np.float32, "normals")
+        if colors is not None:
+            self.colors = self._attribute(colors, np.uint8, "colors")
+
+    def _attribute(self, values, dtype, name):
+        a = np.ascontiguousarray(values, dtype=dtype)
+        if a.shape != self.vertices.shape:
+            raise ValueError("%s: expected %s, one row per vertex, got %s"
+                             % (name, self.vertices.shape, a.shape))
+        return a
 
     @property
     def empty(self):
@@ -66,27 +80,81 @@ class SurfaceMesh(object):
         from .common.mesh_io import get_triangles
         return get_triangles(self.vertices, self.faces)
 
+    # ---- normals and colours (appearance.py) -------------------------
+    def compute_normals(self):
+        """Sets and returns `normals` (n, 3) float32: the unit area-weighted vertex normals,
+        pointing outwards; (0, 0, 0) where the areas around a vertex cancel or it is in no face."""
+        from .appearance import vertex_normals
+        self.normals = vertex_normals(self.vertices, self.faces, unit=True)
+        return self.normals
+
+    def colorize(self, scene, frame_idxs, tol, min_cos=0.0, mode="blend", unseen=(0.5, 0.5, 0.5)):
+        """Sets `colors` (n, 3) uint8 from the images of the scene's frames `frame_idxs` and
+        returns the mask of the views that saw each vertex ([n] uint32, bit k: frame_idxs[k]).
+        A frame sees a vertex that projects into its image, faces it (the vertex normal, computed
+        if absent, at cos > min_cos) and is no farther from its camera than the mesh's own depth
+        map there plus `tol` (scene units; a vertex lies on the surface it is tested against, so
+        tol is the slack for the pixel's footprint -- a voxel diagonal is the natural size).  mode
+        "blend": the cos^2-weighted mean of the frames, "best": the frame that faces the vertex
+        best.  A vertex no frame sees gets `unseen`."""
+        from .appearance import project_colors, scene_views, to_rgb8
+        if self.empty:
+            raise ValueError("the mesh is empty: there is no surface to colour")
+        cameras, images = scene_views(scene, frame_idxs)
+        H, W = np.asarray(images[0]).shape[:2]
+        caster = self.raycaster()
+        depth_maps = [caster.depth_map(cam, H, W) for cam in cameras]
+        if self.normals is None:
+            self.compute_normals()
+        got = project_colors(self.vertices, cameras, images, depth_maps, self.normals, tol=tol,
+                             min_cos=min_cos, mode=mode)
+        self.colors = to_rgb8(got.colors, got.seen, unseen)
+        return got.views
+
     # ---- file ------------------------------------------------------------------------------
     def save_ply(self, path):
-        """A binary little-endian PLY: `vertex` x y z float, `face` one list vertex_indices of
-        uchar 3 and three ints -- the file common.mesh_io.parse_gt_data_from_ply reads back to
-        the same arrays."""
+        """A binary little-endian PLY: `vertex` x y z float -- then nx ny nz float where the mesh
+        has normals and red green blue uchar where it has colours -- and `face` one list
+        vertex_indices of uchar 3 and three ints: the file common.mesh_io.parse_gt_data_from_ply
+        reads back (and `load_ply` restores, attributes included)."""
         rows = np.empty((len(self.faces),), dtype=[("n", "u1"), ("v", "<i4", (3,))])
         rows["n"] = 3
         rows["v"] = self.faces
+        fields, header = [("xyz", "<f4", (3,))], ""
+        if self.normals is not None:
+            fields.append(("normal", "<f4", (3,)))
+            header += "property float nx\nproperty float ny\nproperty float nz\n"
+        if self.colors is not None:
+            fields.append(("rgb", "u1", (3,)))
+            header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
         with open(path, "wb") as f:
             f.write(("ply\nformat binary_little_endian 1.0\ncomment raynet_amd surface mesh\n"
                      "element vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                     "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
-                     % (len(self.vertices), len(self.faces))).encode())
-            self.vertices.astype("<f4").tofile(f)
+                     "%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                     % (len(self.vertices), header, len(self.faces))).encode())
+            if len(fields) == 1:
+                self.vertices.astype("<f4").tofile(f)
+            else:
+                table = np.empty((len(self.vertices),), dtype=fields)
+                table["xyz"] = self.vertices
+                if self.normals is not None:
+                    table["normal"] = self.normals
+                if self.colors is not None:
+                    table["rgb"] = self.colors
+                table.tofile(f)
             rows.tofile(f)
 
     @classmethod
     def load_ply(cls, path):
-        from .common.mesh_io import parse_gt_data_from_ply
+        from .common.mesh_io import parse_gt_data_from_ply, read_ply
         points, _, faces = parse_gt_data_from_ply(path)
-        return cls(points, faces)
+        vertex = read_ply(path)["vertex"]
+        normals = colors = None
+        if all(k in vertex for k in ("nx", "ny", "nz")):
+            normals = np.stack([vertex[k] for k in ("nx", "ny", "nz")], axis=1).astype(np.float32)
+        if all(k in vertex for k in ("red", "green", "blue")):
+            colors = np.stack([vertex[k] for k in ("red", "green", "blue")], axis=1).astype(np.uint8)
+        return cls(points, faces, normals, colors)
 
     # ---- the mesh tools --------------------------------------------------------------------
     def raycaster(self):
