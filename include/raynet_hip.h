@@ -543,7 +543,10 @@ int rn_depthmap_points(rn_ctx *ctx, int32_t H, int32_t W, const double *P_pinv,
 
 /* One neighbour view of raynet/pointcloud.py:205-245: tau[i] = max(tau[i], |depth_map at the
  * point's projection - distance of the point to that camera|), inf where the projection
- * falls outside the view; first != 0 starts tau.  points [3][n] f64, P [3][4]. */
+ * falls outside the view; first != 0 starts tau.  points [3][n] f64, P [3][4].  "Outside" is
+ * decided on the rounded projection as doubles (half to even, 0 <= x < W, 0 <= y < H): a
+ * projection that is NaN, +-inf or beyond any int is outside, never converted to an index.
+ * A NaN depth makes tau NaN (np.maximum) until a view the point is outside of makes it inf. */
 int rn_consistency_tau(rn_ctx *ctx, int32_t n, int32_t H, int32_t W, int32_t first,
                        const double *points, const double *P, const double *camera_center,
                        const float *depth_map, double *tau, void *stream);

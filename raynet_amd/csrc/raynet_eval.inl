@@ -61,10 +61,12 @@ __global__ __launch_bounds__(BLOCK) void k_consistency_tau(int n, int H, int W, 
 #pragma unroll
     for (int k = 0; k < 3; k++)
         h[k] = P[4 * k] * p[0] + P[4 * k + 1] * p[1] + P[4 * k + 2] * p[2] + P[4 * k + 3] * p[3];
-    // np.round (half to even) then int32
-    const int x = (int)rint(h[0] / h[2]), y = (int)rint(h[1] / h[2]);
-    const bool valid = 0 <= x && x < W && 0 <= y && y < H;
-    const double predicted = (double)depth[valid ? (size_t)y * W + x : 0];
+    // np.round (half to even); the range test is made on the doubles: NaN, +-inf and what no int
+    // holds fail it (the reference's int32 cast makes them negative), and only a valid
+    // coordinate is converted
+    const double rx = rint(h[0] / h[2]), ry = rint(h[1] / h[2]);
+    const bool valid = rx >= 0.0 && rx < (double)W && ry >= 0.0 && ry < (double)H;
+    const double predicted = (double)depth[valid ? (size_t)(int)ry * W + (int)rx : 0];
     double dist = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {

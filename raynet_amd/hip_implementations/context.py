@@ -439,20 +439,56 @@ class HipContext(object):
             _ptr(g_S_new), _ptr(g_Sr), _ptr(g_acc), _ptr(g_msgs), _stream()))
 
     # ---- consumers of the depth maps (point clouds, metrics) --------------------------
+    @staticmethod
+    def _chk_view(H, W, camera, n_camera, center, depth_map, name):
+        """One view of the float64 kernels: a [3][4] / [4][3] matrix, a centre of FOUR components
+        (both kernels read center[3]) and an (H, W) f32 depth map."""
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError("H, W: at least 1 and H * W below 2^31, got %d, %d" % (H, W))
+        _chk(camera, torch.float64, n_camera, name, align=8)
+        _chk(center, torch.float64, 4, "center", align=8)
+        _chk(depth_map, torch.float32, H * W, "depth_map")
+        return H, W
+
     def depthmap_points(self, H, W, P_pinv, center, depth_map, points):
-        self._check(self.lib.rn_depthmap_points(self._h, int(H), int(W), _ptr(P_pinv), _ptr(center),
+        """P_pinv [4][3] f64, center [4] f64, depth_map (H, W) f32 -> points (3, H*W) f64, the
+        point of pixel (v, u) at column u*H + v."""
+        H, W = self._chk_view(H, W, P_pinv, 12, center, depth_map, "P_pinv")
+        _chk(points, torch.float64, 3 * H * W, "points", align=8)
+        self._check(self.lib.rn_depthmap_points(self._h, H, W, _ptr(P_pinv), _ptr(center),
                                                 _ptr(depth_map), _ptr(points), _stream()))
 
     def consistency_tau(self, H, W, first, points, P, center, depth_map, tau):
-        self._check(self.lib.rn_consistency_tau(self._h, points.shape[1], int(H), int(W),
-                                                1 if first else 0, _ptr(points), _ptr(P),
-                                                _ptr(center), _ptr(depth_map), _ptr(tau),
+        """points (3, n) f64, P [3][4] f64, center [4] f64, depth_map (H, W) f32, tau [n] f64
+        (read unless `first`, written)."""
+        H, W = self._chk_view(H, W, P, 12, center, depth_map, "P")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] != 3:
+            raise ValueError("points: expected shape (3, n), got %s"
+                             % (tuple(getattr(points, "shape", ())),))
+        n = int(points.shape[1])
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        _chk(tau, torch.float64, n, "tau", align=8)
+        self._check(self.lib.rn_consistency_tau(self._h, n, H, W, 1 if first else 0, _ptr(points),
+                                                _ptr(P), _ptr(center), _ptr(depth_map), _ptr(tau),
                                                 _stream()))
 
     def nearest_neighbors(self, ref_xyzw, query_xyzw, dist, idx=None):
-        self._check(self.lib.rn_nearest_neighbors(self._h, ref_xyzw.shape[0], _ptr(ref_xyzw),
-                                                  query_xyzw.shape[0], _ptr(query_xyzw),
-                                                  _ptr(dist), _ptr(idx), _stream()))
+        """ref_xyzw (n_ref, 4) f32, query_xyzw (n_query, 4) f32 (the fourth lane is not read) ->
+        dist [n_query] f32 and / or idx [n_query] i32 (either may be None, not both)."""
+        for name, t in (("ref_xyzw", ref_xyzw), ("query_xyzw", query_xyzw)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 4:
+                raise ValueError("%s: expected shape (n, 4), got %s"
+                                 % (name, tuple(getattr(t, "shape", ())),))
+            _chk(t, torch.float32, 4 * int(t.shape[0]), name, align=16)
+        n_ref, n_query = int(ref_xyzw.shape[0]), int(query_xyzw.shape[0])
+        if dist is None and idx is None:
+            raise ValueError("dist, idx: at least one output is required")
+        _chk(dist, torch.float32, n_query, "dist", optional=True)
+        _chk(idx, torch.int32, n_query, "idx", optional=True)
+        self._check(self.lib.rn_nearest_neighbors(self._h, n_ref, _ptr(ref_xyzw), n_query,
+                                                  _ptr(query_xyzw), _ptr(dist), _ptr(idx),
+                                                  _stream()))
 
     # ---- point-cloud filters (raynet_amd/metrics.py: VoxelMask, ReduceDensity) ------------
     def voxel_mask(self, points, box, mask, keep):
