@@ -961,6 +961,50 @@ int rn_project_colors(rn_ctx *ctx, int64_t n, const float *points, const float *
                       double border, int32_t mode, float *colors, float *weight, uint32_t *views,
                       void *stream);
 
+/* ---- depth maps fused into a truncated signed distance volume ----
+ *
+ * rn_tsdf_integrate: every view into the context's grid in one launch.  All arrays are device
+ * memory.  cameras [V][15] f64, a row P [3][4] row-major | centre [3] (as for rn_project_colors);
+ * depths [V][H][W] f32, distances to the camera centre, pixel centres at whole coordinates;
+ * weights [V][H][W] f32 or NULL for weight 1.  0 <= V <= 4096 (the bound rejects garbage; it is no
+ * capacity).  Written: tsdf [gx][gy][gz] f32 and weight [gx][gy][gz] f32 over the context's grid --
+ * all G entries, always, also with V == 0; both are finite whatever the inputs hold.
+ *
+ * One thread per voxel; its centre p = (x, y, z) is the context's axis tables (rn_set_voxel_grid)
+ * converted to double; the views v in ascending order.  Every operation is fp64 and rounded on its
+ * own, in the order written (the library is built with -ffp-contract=off); only + - * /, rint, min,
+ * comparisons and conversions occur -- no sqrt -- so a NumPy restatement gives the same bits
+ * (tests/fusion_truth.py):
+ *   projection   h_k = ((P_k0 x + P_k1 y) + P_k2 z) + P_k3;  X = h_0 / h_2;  Y = h_1 / h_2
+ *                d = c - p;  dd = (d_x^2 + d_y^2) + d_z^2    (exactly as rn_project_colors)
+ *   in view      0 < h_2 < inf,  dd > 0,  border <= X <= (W - 1) - border,
+ *                border <= Y <= (H - 1) - border             (a NaN fails every test)
+ *   measurement  z = depths[v][rint(Y)][rint(X)] (half to even); counts only if 0 < z < inf
+ *                (0, a negative value, NaN and +inf are "no measurement")
+ *   weight       w = 1, or w = weights[v][the same pixel]; counts only if 0 < w < inf
+ *   distance     s = (z z - dd) / (z + z)
+ *   behind       the view counts only if s >= -trunc
+ *   value        t = min(s / trunc, 1)
+ *   sums         num = num + w t;  den = den + w
+ *   result       den > 0:  tsdf = (float)(num / den),  weight = (float) den
+ *                else:     tsdf = 1.0f,                weight = 0.0f
+ * A view that does not count reads pixel (0, 0) of its maps, so every load lies inside the arrays
+ * whatever the cameras hold.
+ *
+ * s is (z - r)(z + r) / 2z with r = sqrt(dd), the distance of the voxel from the camera: it is 0
+ * exactly where r = z and monotone in r, so its zero crossing -- all the surface depends on -- is
+ * the true one; it differs from z - r by the factor 1 - (z - r) / 2z, inside the band at most
+ * trunc / 2z; and it needs no sqrt, which is what lets a restatement give the same bits.  tsdf > 0
+ * in front of the surface (free space, 1 at trunc and beyond), < 0 behind it down to -1; a voxel
+ * more than trunc behind every surface it is seen against is unobserved by that view.
+ *
+ * RN_ERR_INVALID, rn_last_error naming the entry, no launch: V outside 0..4096, H or W below 1,
+ * trunc not finite or <= 0, border negative or not finite, a NULL tsdf or weight, a NULL cameras or
+ * depths with V > 0.  RN_ERR_STATE before rn_set_voxel_grid. */
+int rn_tsdf_integrate(rn_ctx *ctx, int32_t V, const double *cameras, int32_t H, int32_t W,
+                      const float *depths, const float *weights, double trunc, double border,
+                      float *tsdf, float *weight, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

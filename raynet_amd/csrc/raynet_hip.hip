@@ -1238,5 +1238,8 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // section 20)
 #include "raynet_appearance.inl"
 
+// depth maps fused into a truncated signed distance volume
+#include "raynet_fusion.inl"
+
 // the surface of a belief grid: marching tetrahedra and the grid-level scan
 #include "raynet_isosurface.inl"

@@ -380,6 +380,32 @@ class HipContext(object):
             _ptr(depths), float(tol), float(min_cos), float(border), int(mode), _ptr(colors),
             _ptr(weight), _ptr(views), _stream()))
 
+    # ---- depth maps into a TSDF volume (raynet_amd/fusion.py) --------------------------------
+    def tsdf_integrate(self, cameras, depths, weights, trunc, border, tsdf=None, weight=None):
+        """rn_tsdf_integrate: cameras (V, 15) f64, depths (V, H, W) f32 of distances to the camera
+        centres, weights (V, H, W) f32 or None -> (tsdf, weight), both [gx][gy][gz] f32 over the
+        context's grid: the weighted mean of the views' truncated signed distances (in units of
+        `trunc`, 1 in free space) and the sum of their weights; 1 and 0 where no view counts."""
+        if depths.dim() != 3 or weights is not None and weights.shape != depths.shape:
+            raise ValueError("depths: expected (V, H, W) and weights of the same shape, got %s, %s"
+                             % (tuple(depths.shape), None if weights is None else tuple(weights.shape)))
+        V, H, W = (int(s) for s in depths.shape)
+        if cameras.dim() != 2 or tuple(cameras.shape) != (V, 15):
+            raise ValueError("cameras: expected (%d, 15), got %s" % (V, tuple(cameras.shape)))
+        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
+        _chk(depths, torch.float32, V * H * W, "depths")
+        _chk(weights, torch.float32, V * H * W, "weights", optional=True)
+        if tsdf is None:
+            tsdf = torch.empty(self.grid_shape, dtype=torch.float32, device=depths.device)
+        if weight is None:
+            weight = torch.empty(self.grid_shape, dtype=torch.float32, device=depths.device)
+        _chk(tsdf, torch.float32, self.G, "tsdf")
+        _chk(weight, torch.float32, self.G, "weight")
+        self._check(self.lib.rn_tsdf_integrate(
+            self._h, V, _ptr(cameras), H, W, _ptr(depths), _ptr(weights), float(trunc),
+            float(border), _ptr(tsdf), _ptr(weight), _stream()))
+        return tsdf, weight
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

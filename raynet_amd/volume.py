@@ -80,6 +80,22 @@ class SurfaceMesh(object):
         from .common.mesh_io import get_triangles
         return get_triangles(self.vertices, self.faces)
 
+    def without_nonfinite(self):
+        """-> a new SurfaceMesh without the faces that have a vertex with a non-finite component
+        and without the vertices no remaining face names, renumbered; the order of faces and
+        vertices is kept, normals and colours go along.  (The iso-surface of a field with NaN
+        entries has such vertices: HipContext.isosurface, fusion.TSDFVolume.mesh.)"""
+        vertices, faces = torch.from_numpy(self.vertices), torch.from_numpy(self.faces).long()
+        finite = torch.isfinite(vertices).all(1)
+        faces = faces[finite[faces].all(1)]
+        used = torch.zeros(len(vertices), dtype=torch.bool)
+        used[faces.reshape(-1)] = True
+        new = torch.cumsum(used, 0) - 1
+        keep = used.numpy()
+        return SurfaceMesh(self.vertices[keep], new[faces].to(torch.int32).numpy(),
+                           None if self.normals is None else self.normals[keep],
+                           None if self.colors is None else self.colors[keep])
+
     # ---- normals and colours (appearance.py, DESIGN.md section 20) -------------------------
     def compute_normals(self):
         """Sets and returns `normals` (n, 3) float32: the unit area-weighted vertex normals,
