@@ -1005,6 +1005,43 @@ int rn_tsdf_integrate(rn_ctx *ctx, int32_t V, const double *cameras, int32_t H, 
                       const float *depths, const float *weights, double trunc, double border,
                       float *tsdf, float *weight, void *stream);
 
+/* ---- the connected components of an indexed triangle mesh ----
+ *
+ * rn_mesh_components: which piece every vertex belongs to, and how large the pieces are.  Two
+ * vertices are connected if a face names both; a component is a class of the transitive closure.
+ * Positions play no part, and the entry does not take them: two pieces that touch only in space,
+ * with duplicated vertex rows, are two components.  (The marching-tetrahedra meshes of
+ * rn_isosurface_emit share one vertex per lattice edge, so for them "connected" is what one
+ * expects.)
+ *
+ * All arrays are device memory.  faces [nf][3] i32; labels, vertex_counts and face_counts [nv] i32,
+ * written in all nv entries, always; status [1] i32.  vertex_counts, face_counts and status may
+ * each be NULL: not wanted.
+ *   labels[v]         the smallest vertex index of v's component; a vertex in no face is its own
+ *                     component.  Hence labels[v] <= v and labels[labels[v]] == labels[v], and the
+ *                     result is one fixed array whatever the launch geometry or the order in which
+ *                     the hardware ran the threads.
+ *   vertex_counts[r]  the number of vertices with label r
+ *   face_counts[r]    the number of counted faces whose first vertex has label r
+ * Both counts are 0 at every r that is not a label; they are integers added by integer atomics,
+ * so they are exact.
+ *
+ * A face with any index outside [0, nv) is skipped as a whole: it connects nothing and is counted
+ * nowhere; whatever `faces` holds, nothing is read or written out of bounds.  Degenerate faces
+ * count like any other: (a, a, b) connects a and b, (a, a, a) connects nothing; duplicate faces
+ * count once each.
+ *
+ * status[0] is 0 after every correct run, 1 if a pointer chase of the union-find reached its bound
+ * of nv + 1 steps -- which cannot happen while parent[x] <= x holds; it exists so
+ * that a bug ends as an error and not as a hang.
+ *
+ * nv == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch, outputs
+ * untouched: nv or nf negative, nv > 2^31 - 2, 3 nf > 2^31 - 1, a NULL labels, a NULL faces with
+ * nf > 0. */
+int rn_mesh_components(rn_ctx *ctx, int64_t nv, int64_t nf, const int32_t *faces,
+                       int32_t *labels, int32_t *vertex_counts, int32_t *face_counts,
+                       int32_t *status, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

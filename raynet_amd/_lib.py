@@ -48,6 +48,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_appearance.inl"),
             os.path.join(CSRC, "raynet_appearance_args.h"),
             os.path.join(CSRC, "raynet_fusion.inl"), os.path.join(CSRC, "raynet_fusion_args.h"),
+            os.path.join(CSRC, "raynet_components.inl"),
+            os.path.join(CSRC, "raynet_components_args.h"),
             HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
@@ -216,6 +218,7 @@ SIGNATURES = {
     "rn_vertex_area_normals": [_P, _L, _P, _L, _P, _P, _P, _P, _P],
     "rn_project_colors": [_P, _L, _P, _P, _I, _P, _I, _I, _I, _P, _P, _D, _D, _D, _I, _P, _P, _P, _P],
     "rn_tsdf_integrate": [_P, _I, _P, _I, _I, _P, _P, _D, _D, _P, _P, _P],
+    "rn_mesh_components": [_P, _L, _L, _P, _P, _P, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

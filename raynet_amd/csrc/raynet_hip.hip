@@ -1241,5 +1241,8 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // depth maps fused into a truncated signed distance volume
 #include "raynet_fusion.inl"
 
+// the connected components of a surface mesh: a lock-free union-find
+#include "raynet_components.inl"
+
 // the surface of a belief grid: marching tetrahedra and the grid-level scan
 #include "raynet_isosurface.inl"

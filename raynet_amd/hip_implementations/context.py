@@ -406,6 +406,37 @@ class HipContext(object):
             float(border), _ptr(tsdf), _ptr(weight), _stream()))
         return tsdf, weight
 
+    # ---- connected components of a mesh (raynet_amd/components.py) ---------------------------
+    def mesh_components(self, faces, n_vertices, labels=None, vertex_counts=None, face_counts=None):
+        """rn_mesh_components: faces (nf, 3) i32 of a mesh with `n_vertices` vertices -> (labels,
+        vertex_counts, face_counts), each [nv] i32: the smallest vertex index of every vertex's
+        component (two vertices are connected if a face names both), and at every label the
+        numbers of its vertices and of its faces (0 elsewhere).  A face with an index outside
+        [0, nv) connects and counts nothing.  Synchronises the stream once (the status word comes
+        back: RaynetHipError if the union-find reached a bound, which no input can cause)."""
+        nv = int(n_vertices)
+        if nv < 0:
+            raise ValueError("n_vertices: 0 or more, got %d" % nv)
+        if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+            raise ValueError("faces: expected a (nf, 3) tensor, got %s" % (
+                tuple(faces.shape) if isinstance(faces, torch.Tensor) else type(faces).__name__,))
+        nf = len(faces)
+        _chk(faces, torch.int32, 3 * nf, "faces")
+        outs = []
+        for t, name in ((labels, "labels"), (vertex_counts, "vertex_counts"),
+                        (face_counts, "face_counts")):
+            if t is None:
+                t = torch.empty((nv,), dtype=torch.int32, device=faces.device)
+            outs.append(_chk(t, torch.int32, nv, name))
+        status = torch.zeros((1,), dtype=torch.int32, device=faces.device)
+        self._check(self.lib.rn_mesh_components(self._h, nv, nf, _ptr(faces), _ptr(outs[0]),
+                                                _ptr(outs[1]), _ptr(outs[2]), _ptr(status),
+                                                _stream()))
+        if int(status.item()) != 0:
+            raise _lib.RaynetHipError("rn_mesh_components: a pointer chase reached its bound "
+                                      "(nv %d, nf %d): the labels are not to be used" % (nv, nf))
+        return tuple(outs)
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

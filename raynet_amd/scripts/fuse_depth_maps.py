@@ -28,6 +28,10 @@ observation ends.
 --mesh_cloud PATH --mesh_samples N [--seed S]
                      also write N area-weighted points of the surface as a point cloud, the form
                      compute_metrics scores
+--min_component_faces N, --min_component_fraction X, --keep_largest K
+                     drop the floaters first: the connected components of the mesh with fewer than
+                     N faces, with fewer than X times the largest one's faces, all but the K
+                     largest (raynet_amd.components; before normals, colours and --mesh_cloud)
 """
 import argparse
 import os
@@ -35,6 +39,7 @@ import sys
 
 import numpy as np
 
+from . import component_flags
 from .convert_to_pointcloud import find_format
 
 
@@ -71,6 +76,7 @@ def build_parser():
     p.add_argument("--mesh_samples", type=int, default=None,
                    help="--mesh_cloud: how many area-weighted points to draw")
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
+    component_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.render_volume
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -106,6 +112,7 @@ def main(argv=None):
         parser.error("--min_confidence goes with --confidence_weights")
     if args.gt and args.confidence_weights:
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
+    component_flags.check(parser, args)
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
 
@@ -146,7 +153,7 @@ def main(argv=None):
                         weights=weights, border=args.border)
     if args.volume:
         volume.save(args.volume)
-    mesh = volume.mesh(args.min_weight)
+    mesh = component_flags.apply(volume.mesh(args.min_weight), args)
     if (args.normals or args.color or args.mesh_cloud) and mesh.empty:
         parser.error("the fused surface is empty: no voxel pair straddles a measured depth")
     if args.normals or args.color:

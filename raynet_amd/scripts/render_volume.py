@@ -30,12 +30,19 @@ blend (default) takes the cos^2-weighted mean of the frames, best the frame that
 best.  --depth_tolerance is the slack of the occlusion test in voxel diagonals (default 1: a
 vertex lies on an edge of a lattice cell, and the surface point its nearest pixel records lies in
 the same or the next cell unless the view is grazing).
+
+--min_component_faces N, --min_component_fraction X, --keep_largest K, with --mesh: drop the
+floaters first -- the connected components of the mesh with fewer than N faces, with fewer than X
+times the largest one's faces, all but the K largest (raynet_amd.components) -- before colours and
+--mesh_cloud.
 """
 import argparse
 import os
 import sys
 
 import numpy as np
+
+from . import component_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -71,6 +78,7 @@ def build_parser():
                    help="--color: the weighted mean of the frames that see a vertex, or the best one")
     p.add_argument("--depth_tolerance", type=float, default=1.0,
                    help="--color: the slack of the occlusion test, in voxel diagonals")
+    component_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -99,6 +107,10 @@ def main(argv=None):
         parser.error("--color goes with --mesh PATH: the colours are the mesh's")
     if not (args.depth_tolerance >= 0.0 and args.depth_tolerance < float("inf")):
         parser.error("--depth_tolerance takes a finite number of voxel diagonals, 0 or more")
+    component_flags.check(parser, args)
+    if component_flags.given(args) and not args.mesh:
+        parser.error("--%s goes with --mesh PATH: the components are the mesh's"
+                     % component_flags.given(args)[0])
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -126,7 +138,7 @@ def main(argv=None):
     if args.ply:
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
     if args.mesh or args.mesh_cloud:
-        mesh = volume.mesh(args.threshold, closed=not args.open)
+        mesh = component_flags.apply(volume.mesh(args.threshold, closed=not args.open), args)
         if args.mesh and args.color:
             if mesh.empty or not frames:
                 parser.error("--color: %s" % ("the surface is empty" if mesh.empty else

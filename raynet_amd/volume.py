@@ -96,6 +96,47 @@ class SurfaceMesh(object):
                            None if self.normals is None else self.normals[keep],
                            None if self.colors is None else self.colors[keep])
 
+    # ---- connected components (components.py) ------------------------
+    def components(self):
+        """-> components.MeshComponents: the pieces of the mesh -- two vertices are connected if
+        a face names both (positions play no part) -- in the order of their smallest vertex, with
+        their vertex and face counts."""
+        from . import components
+        if len(self.vertices) == 0:
+            none = np.zeros(0, np.int32)
+            return components.MeshComponents(none, none, none)
+        return components.mesh_components(self.faces, len(self.vertices))
+
+    def keep_components(self, ids_or_mask):
+        """-> a new SurfaceMesh of the components named by `ids_or_mask` (dense ids of
+        `components()`, or a boolean mask over them): their faces and the vertices those name,
+        renumbered; the order of faces and vertices is kept, normals and colours go along."""
+        from . import components
+        if self.empty:
+            return components.keep_faces(self, np.zeros(0, bool))
+        found = self.components()
+        which = np.asarray(ids_or_mask)
+        if which.dtype == bool:
+            if which.shape != (len(found),):
+                raise ValueError("a mask over the components has %d entries, got %s"
+                                 % (len(found), which.shape))
+            keep = which
+        else:
+            ids = which.astype(np.int64).reshape(-1)
+            if len(ids) and (ids.min() < 0 or ids.max() >= len(found)):
+                raise ValueError("a component id outside 0..%d" % (len(found) - 1))
+            keep = np.zeros(len(found), bool)
+            keep[ids] = True
+        return components.keep_faces(self, found.face_mask(self.faces, keep))
+
+    def without_small_components(self, min_faces=None, min_fraction=None, keep_largest=None):
+        """-> a new SurfaceMesh without the floaters: only the components stay that have at least
+        `min_faces` faces, at least `min_fraction` of the largest component's faces, and are among
+        the `keep_largest` largest by faces (ties to the one with the lower first vertex) --
+        every criterion that is given.  Order, normals and colours as for `keep_components`."""
+        from . import components
+        return components.filter_small(self, min_faces, min_fraction, keep_largest)[0]
+
     # ---- normals and colours (appearance.py, DESIGN.md section 20) -------------------------
     def compute_normals(self):
         """Sets and returns `normals` (n, 3) float32: the unit area-weighted vertex normals,
