@@ -50,7 +50,9 @@ def _ray_messages(s, a, m):
     T = np.concatenate([[1.0], np.cumprod(q)[:-1]])
     w = o * T * s
     C = np.concatenate([[0.0], np.cumsum(w)[:-1]])
-    U = np.cumsum(w[::-1])[::-1] - w
+    # sum_{j>i} w_j summed directly: (inclusive suffix) - w_i cancels in the last entries, and
+    # U / q magnifies that by up to 1e4 (enough to drown a finite difference of the messages)
+    U = np.concatenate([np.cumsum(w[::-1])[::-1][1:], [0.0]])
     pos = C + T * s
     neg = C + U / q
     return np.log(pos) - np.log(neg), dict(sig=sig, o=o, q=q, T=T, w=w, C=C, U=U, pos=pos, neg=neg)

@@ -9,10 +9,10 @@ from test_mrf_backward import make_problem
 pytestmark = pytest.mark.gpu
 
 
-def _setup(oracle_mod, **kw):
+def _setup(oracle_mod, problem=make_problem, **kw):
     import torch
     from raynet_amd.mrf import mrf_train
-    o, vg, starts, ends, rvi, rvc, S, planes = make_problem(oracle_mod, **kw)
+    o, vg, starts, ends, rvi, rvc, S, planes = problem(oracle_mod, **kw)
     bbox = np.array([-1, -1, -1, 1, 1, 1], np.float32)
     hip = mrf_train.training_context(rvi.shape[1], S.shape[1], bbox, o.grid_shape, vg)
     dev = dict(rvi=torch.from_numpy(rvi).cuda(), rvc=torch.from_numpy(rvc).cuda(),
@@ -20,13 +20,58 @@ def _setup(oracle_mod, **kw):
     return o, vg, starts, ends, rvi, rvc, S, planes, hip, dev
 
 
-def test_plane_weights_match_oracle(oracle_mod):
+def crossing_problem(oracle_mod, D, M=256, grid=(96, 96, 96)):
+    """Real geometry for rows of one to four chunks of 64: ~32 rays through a 96^3 grid -- along
+    each axis (about 96 voxels), near-diagonals (up to ~250), corner cutters (below 64) and one
+    ray that misses the box -- traversed by the oracle."""
+    rng = np.random.default_rng(96)
+    bbox = np.array([-1, -1, -1, 1, 1, 1], np.float32)
+    o = oracle_mod.Oracle(M=M, D=D, N=2, F=4, H=4, W=4, padding=3, bbox=bbox, grid_shape=grid)
+    vg = oracle_mod.voxel_grid_centers(bbox, grid)
+    rays = []
+    for k in range(31):
+        a = k % 3
+        b, c = (a + 1) % 3, (a + 2) % 3
+        p, q = np.zeros(3), np.zeros(3)
+        p[a], q[a] = -1.0, 1.0
+        if k < 9:                                   # along axis a, a slight slope
+            p[b], p[c] = rng.random(2) * 1.6 - 0.8
+            q[b], q[c] = p[b] + 0.05 * rng.random(), p[c] - 0.03 * rng.random()
+        elif k < 21:                                # near-diagonals of growing slope
+            f = (k - 8) / 12.0
+            p[b], q[b] = -0.8 * f, 0.75 * f
+            p[c], q[c] = 0.1 + 0.3 * rng.random(), 0.1 - 0.4 * f
+        else:                                       # cut a corner: in through a, out through b
+            w = 0.15 + 0.04 * (k - 21)
+            p[b], p[c] = 1.0 - w * 0.7, rng.random() - 0.5
+            q[a], q[b], q[c] = -1.0 + w, 1.0, p[c] + 0.02
+        rays.append((p, q))
+    rays.append((np.full(3, 5.0), np.full(3, 5.0)))    # outside the box: count 0
+    starts = np.array([r[0] for r in rays], np.float32)
+    ends = np.array([r[1] for r in rays], np.float32)
+    rvi, rvc = o.traversal(starts, ends)
+    assert rvc[-1] == 0 and 1 < rvc[:-1].min() < 64 and 192 < rvc.max() <= M, rvc
+    assert ((rvc > 64) & (rvc <= 128)).any() and ((rvc > 128) & (rvc <= 192)).any(), rvc
+    S = rng.random((len(rays), D)) ** 3 + 0.02
+    S /= S.sum(1, keepdims=True)
+    planes = o.plane_indices(vg, rvi, rvc, starts, ends)
+    return o, vg, starts, ends, rvi, rvc, S, planes
+
+
+@pytest.mark.parametrize("D", [None, 2, 3, 12, 64, 256], ids=lambda D: "small" if D is None else "D%d" % D)
+def test_plane_weights_match_oracle(oracle_mod, D):
+    """D None: make_problem (every row inside one wavefront).  Otherwise crossing_problem: the
+    monotone walk's carry from chunk to chunk (carry = lane63i(left)) on rows up to four chunks."""
     import torch
     from raynet_amd.mrf import mrf_train
     from oracle import mrf_backward as mb
-    o, vg, starts, ends, rvi, rvc, S, planes, hip, dev = _setup(oracle_mod)
+    if D is None:
+        o, vg, starts, ends, rvi, rvc, S, planes, hip, dev = _setup(oracle_mod)
+    else:
+        o, vg, starts, ends, rvi, rvc, S, planes, hip, dev = _setup(oracle_mod, problem=crossing_problem, D=D)
     left, c1, c2 = mrf_train.plane_weights(hip, dev["rvi"], dev["rvc"], dev["starts"], dev["ends"])
     left, c1, c2 = left.cpu().numpy(), c1.cpu().numpy(), c2.cpu().numpy()
+    assert left.min() >= 0 and left.max() <= S.shape[1] - 2        # left + 1 stays inside the column
     for r in range(len(rvc)):
         c = int(rvc[r])
         assert np.array_equal(left[r, :c], planes[r, :c])          # bit-exact index work
@@ -46,12 +91,18 @@ def test_plane_weights_match_oracle(oracle_mod):
     assert np.abs(x.cpu().numpy() - Sv).max() < 1e-6
 
 
-@pytest.mark.parametrize("seed,iters", [(0, 3), (1, 3), (2, 1), (4, 0)])
-def test_forward_and_backward_match_float64(oracle_mod, seed, iters):
+# rows of up to two chunks, with the planes of the oracle (not of the kernel under test)
+LONG_ROWS = dict(grid=(48, 48, 48), M=160, D=24)
+
+
+@pytest.mark.parametrize("seed,iters,kw", [(0, 3, {}), (1, 3, {}), (2, 1, {}), (4, 0, {}), (6, 3, LONG_ROWS)],
+                         ids=["0-3", "1-3", "2-1", "4-0", "long-rows"])
+def test_forward_and_backward_match_float64(oracle_mod, seed, iters, kw):
     import torch
     from raynet_amd.mrf import mrf_train
     from oracle import mrf_backward as mb
-    o, vg, starts, ends, rvi, rvc, S, planes, hip, dev = _setup(oracle_mod, seed=seed)
+    o, vg, starts, ends, rvi, rvc, S, planes, hip, dev = _setup(oracle_mod, seed=seed, **kw)
+    assert not kw or rvc.max() > 64
     rng = np.random.default_rng(50 + seed)
     G = rng.standard_normal((len(S), rvi.shape[1]))
     gamma = 0.05
