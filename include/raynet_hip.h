@@ -1042,6 +1042,66 @@ int rn_mesh_components(rn_ctx *ctx, int64_t nv, int64_t nf, const int32_t *faces
                        int32_t *labels, int32_t *vertex_counts, int32_t *face_counts,
                        int32_t *status, void *stream);
 
+/* ---- Taubin smoothing of an indexed triangle mesh ----
+ *
+ * rn_mesh_smooth: the vertices of a mesh moved towards the mean of their neighbours and back
+ * (Taubin's lambda | mu scheme), so that the terraces of an iso-surface and the noise of a fused
+ * one flatten while the surface keeps its size.  The faces do not change.
+ *
+ * All arrays are device memory.  vertices_in and vertices_out [nv][3] f32; faces [nf][3] i32;
+ * offsets [nv + 1] i32 and corners [3 nf] i32: the corner table of rn_vertex_area_normals; fixed
+ * [nv] u8 or NULL: a non-zero entry pins that vertex; workspace: 8-byte aligned, at least
+ * rn_mesh_smooth_workspace_bytes(ctx, nv, nf) bytes (-1 for sizes rn_mesh_smooth refuses), laid
+ * out ring [3 nf][2] i32 | scratch [nv][3] f32.  Nothing beyond that size is touched.
+ *
+ * The ring, written once per call, one thread per table position k in [0, 3 nf):
+ *     c = corners[k];  f = c / 3;  slot = c % 3
+ *     ring[2k] = faces[f][(slot + 1) % 3];  ring[2k + 1] = faces[f][(slot + 2) % 3]
+ * both -1 instead if c is outside [0, 3 nf) or any of the face's three indices is outside [0, nv).
+ *
+ * One step with factor t from src to dst, one thread per vertex v.  Every operation is fp64 and
+ * rounded on its own, in the order written (the library is built with -ffp-contract=off); only
+ * + - * /, comparisons and conversions occur, so a NumPy restatement gives the same bits
+ * (tests/smooth_truth.py):
+ *     p = (double) src[v];  s = 0;  m = 0
+ *     for k = offsets[v] .. offsets[v + 1] - 1, the range cut to [0, 3 nf), ascending:
+ *         a = ring[2k];  b = ring[2k + 1];  if a < 0: continue
+ *         s = (s + (double) src[a]) + (double) src[b]          per coordinate
+ *         m = m + 2
+ *     if m == 0 or (fixed and fixed[v]):  dst[v] = src[v]      (the bits)
+ *     else:  x = p + t * (s / (double) m - p)                  per coordinate
+ *            lo = (double) in[v] - max_move;  hi = (double) in[v] + max_move
+ *            if x < lo: x = lo;   if x > hi: x = hi            (a NaN passes both tests)
+ *            dst[v] = (float) x
+ * Every incident triangle gives its two other vertices: on a closed manifold mesh each neighbour
+ * appears in two triangles and this is the uniform umbrella operator; at an open border the border
+ * neighbours weigh half, which is what `fixed` is for.
+ *
+ * An iteration is a step with lambda, then a step with mu if mu != 0 (mu == 0: plain Laplacian
+ * smoothing): L = iterations * (mu != 0 ? 2 : 1) launches that ping-pong between the scratch and
+ * vertices_out, the parity such that step L writes vertices_out.  Positions are f32 between steps.
+ * vertices_in is never written and the clamp always refers to it: no coordinate of any vertex ends
+ * farther than max_move from where it started; +inf: no clamp.  iterations == 0 copies vertices_in
+ * to vertices_out and launches nothing.  No step reads a buffer that another thread of the same
+ * launch writes, so the result is one fixed array whatever the order the hardware ran the threads
+ * in.
+ *
+ * Whatever the three index arrays hold, nothing is read or written out of bounds, and no index
+ * depends on a floating-point value.  A non-finite position spreads to its neighbours and nowhere
+ * else; callers clean first (SurfaceMesh.without_nonfinite).
+ *
+ * nv == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch, outputs
+ * untouched: nv or nf negative, nv > 2^31 - 2, 3 nf > 2^31 - 1, iterations outside 0..10000,
+ * lambda not finite or outside (0, 1], mu not finite or outside [-1, 0], max_move NaN or <= 0, a
+ * NULL vertices_in / offsets / vertices_out / workspace, a NULL faces / corners with nf > 0, a
+ * workspace that is not 8-byte aligned, vertices_out == vertices_in, either of them equal to
+ * workspace. */
+int64_t rn_mesh_smooth_workspace_bytes(rn_ctx *ctx, int64_t nv, int64_t nf);
+int rn_mesh_smooth(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t nf,
+                   const int32_t *faces, const int32_t *offsets, const int32_t *corners,
+                   const uint8_t *fixed, int32_t iterations, double lambda, double mu,
+                   double max_move, void *workspace, float *vertices_out, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

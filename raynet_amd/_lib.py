@@ -50,6 +50,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_fusion.inl"), os.path.join(CSRC, "raynet_fusion_args.h"),
             os.path.join(CSRC, "raynet_components.inl"),
             os.path.join(CSRC, "raynet_components_args.h"),
+            os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
             HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
@@ -219,6 +220,8 @@ SIGNATURES = {
     "rn_project_colors": [_P, _L, _P, _P, _I, _P, _I, _I, _I, _P, _P, _D, _D, _D, _I, _P, _P, _P, _P],
     "rn_tsdf_integrate": [_P, _I, _P, _I, _I, _P, _P, _D, _D, _P, _P, _P],
     "rn_mesh_components": [_P, _L, _L, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_smooth_workspace_bytes": [_P, _L, _L],
+    "rn_mesh_smooth": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],
@@ -255,5 +258,6 @@ def load():
     lib.rn_acc_size.restype = ctypes.c_int64
     lib.rn_slab_boxes_size.restype = ctypes.c_int64
     lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
+    lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib

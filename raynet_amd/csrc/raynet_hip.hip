@@ -1244,5 +1244,8 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // the connected components of a surface mesh: a lock-free union-find
 #include "raynet_components.inl"
 
+// Taubin smoothing of a surface mesh: a gather over the corner table
+#include "raynet_smooth.inl"
+
 // the surface of a belief grid: marching tetrahedra and the grid-level scan
 #include "raynet_isosurface.inl"

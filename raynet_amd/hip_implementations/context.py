@@ -437,6 +437,40 @@ class HipContext(object):
                                       "(nv %d, nf %d): the labels are not to be used" % (nv, nf))
         return tuple(outs)
 
+    # ---- Taubin smoothing of a mesh (raynet_amd/smoothing.py) ---------------------------------
+    def mesh_smooth_workspace_bytes(self, nv, nf):
+        """rn_mesh_smooth_workspace_bytes: the bytes rn_mesh_smooth needs for nv vertices, nf faces."""
+        n = int(self.lib.rn_mesh_smooth_workspace_bytes(self._h, int(nv), int(nf)))
+        if n < 0:
+            raise ValueError("rn_mesh_smooth_workspace_bytes: bad sizes (nv %d, nf %d)" % (nv, nf))
+        return n
+
+    def mesh_smooth(self, vertices, faces, offsets, corners, fixed=None, iterations=10, lam=0.5,
+                    mu=-0.53, max_move=float("inf"), workspace=None, out=None):
+        """rn_mesh_smooth: vertices (nv, 3) f32, faces (nf, 3) i32, the corner table (offsets
+        [nv + 1] i32, corners [3 nf] i32), fixed [nv] u8 or None -> (nv, 3) f32: `iterations`
+        Taubin iterations (a step with `lam`, then one with `mu` unless it is 0), no coordinate
+        farther than `max_move` from where it started.  workspace: a uint8 tensor of at least
+        mesh_smooth_workspace_bytes(nv, nf) bytes, 8-byte aligned (allocated if None)."""
+        nv, nf = len(vertices), len(faces)
+        _chk(vertices, torch.float32, 3 * nv, "vertices")
+        _chk(faces, torch.int32, 3 * nf, "faces")
+        _chk(offsets, torch.int32, nv + 1, "offsets")
+        _chk(corners, torch.int32, 3 * nf, "corners")
+        _chk(fixed, torch.uint8, nv, "fixed", optional=True, align=1)
+        need = self.mesh_smooth_workspace_bytes(nv, nf)
+        if workspace is None:
+            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
+        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        if out is None:
+            out = torch.empty((nv, 3), dtype=torch.float32, device=vertices.device)
+        _chk(out, torch.float32, 3 * nv, "out")
+        self._check(self.lib.rn_mesh_smooth(
+            self._h, nv, _ptr(vertices), nf, _ptr(faces), _ptr(offsets), _ptr(corners), _ptr(fixed),
+            int(iterations), float(lam), float(mu), float(max_move), _ptr(workspace), _ptr(out),
+            _stream()))
+        return out
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

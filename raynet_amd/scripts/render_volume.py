@@ -35,6 +35,11 @@ the same or the next cell unless the view is grazing).
 floaters first -- the connected components of the mesh with fewer than N faces, with fewer than X
 times the largest one's faces, all but the K largest (raynet_amd.components) -- before colours and
 --mesh_cloud.
+
+--smooth N [--smooth_lambda L --smooth_mu M --smooth_max_move X --smooth_free_boundary], with
+--mesh: then smooth the surface -- N Taubin iterations, no coordinate moved farther than X sides of
+the smallest voxel (default 1), the border of an --open mesh pinned (raynet_amd.smoothing) --
+before colours and --mesh_cloud.
 """
 import argparse
 import os
@@ -42,7 +47,7 @@ import sys
 
 import numpy as np
 
-from . import component_flags
+from . import component_flags, smooth_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -79,6 +84,7 @@ def build_parser():
     p.add_argument("--depth_tolerance", type=float, default=1.0,
                    help="--color: the slack of the occlusion test, in voxel diagonals")
     component_flags.add_arguments(p)
+    smooth_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -111,6 +117,10 @@ def main(argv=None):
     if component_flags.given(args) and not args.mesh:
         parser.error("--%s goes with --mesh PATH: the components are the mesh's"
                      % component_flags.given(args)[0])
+    smooth_flags.check(parser, args)
+    if smooth_flags.given(args) and not args.mesh:
+        parser.error("--%s goes with --mesh PATH: the smoothing is the mesh's"
+                     % smooth_flags.given(args)[0])
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -139,12 +149,13 @@ def main(argv=None):
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
     if args.mesh or args.mesh_cloud:
         mesh = component_flags.apply(volume.mesh(args.threshold, closed=not args.open), args)
+        bbox = volume.bbox.astype(np.float64)
+        voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
+        mesh = smooth_flags.apply(mesh, args, voxel)
         if args.mesh and args.color:
             if mesh.empty or not frames:
                 parser.error("--color: %s" % ("the surface is empty" if mesh.empty else
                                               "--start_end selects no frame of the scene"))
-            bbox = volume.bbox.astype(np.float64)
-            voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
             mesh.compute_normals()
             mesh.colorize(scene, frames, tol=args.depth_tolerance * float(np.sqrt((voxel ** 2).sum())),
                           mode=args.color_mode)

@@ -137,6 +137,25 @@ class SurfaceMesh(object):
         from . import components
         return components.filter_small(self, min_faces, min_fraction, keep_largest)[0]
 
+    # ---- smoothing (smoothing.py) -------------------------------------
+    def smoothed(self, iterations=10, lam=0.5, mu=-0.53, fixed="boundary", max_move=None):
+        """-> a new SurfaceMesh with the vertices after `iterations` Taubin iterations
+        (smoothing.smooth_vertices: the keywords are its own): the terraces of an iso-surface and
+        the noise of a fused surface flatten, the surface keeps its size.  The faces and their
+        order stay, colours go along, normals are recomputed if and only if this mesh has them.
+        An empty mesh gives an empty mesh, without the GPU."""
+        from . import smoothing
+        if self.empty:
+            smoothing.check_parameters(iterations, float(lam), float(mu),
+                                       float("inf") if max_move is None else float(max_move))
+            return SurfaceMesh(self.vertices.copy(), self.faces.copy(), self.normals, self.colors)
+        out = SurfaceMesh(smoothing.smooth_vertices(self.vertices, self.faces, iterations, lam, mu,
+                                                    fixed, max_move),
+                          self.faces.copy(), None, self.colors)
+        if self.normals is not None:
+            out.compute_normals()
+        return out
+
     # ---- normals and colours (appearance.py, DESIGN.md section 20) -------------------------
     def compute_normals(self):
         """Sets and returns `normals` (n, 3) float32: the unit area-weighted vertex normals,
