@@ -1102,6 +1102,71 @@ int rn_mesh_smooth(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t nf
                    const uint8_t *fixed, int32_t iterations, double lambda, double mu,
                    double max_move, void *workspace, float *vertices_out, void *stream);
 
+/* ---- vertex clustering of an indexed triangle mesh on a uniform grid ----
+ *
+ * rn_mesh_simplify: the vertices of a mesh that share a cell of a uniform grid become one vertex at
+ * their mean; faces that lose a corner that way vanish, vertices no face is left for vanish with
+ * them (Rossignac and Borrel's vertex clustering).
+ *
+ * origin [3] f64, cell [3] f64 and dims [3] i32 are HOST arrays: the grid's corner, the sides of a
+ * cell and the number of cells per axis.  All other arrays are device memory.  vertices_in [nv][3]
+ * f32 and faces_in [nf][3] i32 are never written.  The caller allocates the upper bounds:
+ *   vertices_out [nv][3] f32   the output vertices
+ *   faces_out    [nf][3] i32   the output faces, of output indices
+ *   source       [nv]    i32   the smallest input index of each output vertex's cluster
+ *   cluster      [nv]    i32   the output index of each input vertex's cluster, -1 if unused
+ *   counts       [2]     i64   nv_out, nf_out
+ * Only the first nv_out rows of vertices_out and source and the first nf_out rows of faces_out are
+ * written, and all nv entries of cluster; the rest keep their bits.  source and cluster may each be
+ * NULL: not wanted.  workspace: 8-byte aligned, at least rn_mesh_simplify_workspace_bytes(nv, nf,
+ * dims) bytes (-1 for sizes or dims rn_mesh_simplify refuses), laid out table [cells][4] u64 (S_x,
+ * S_y, S_z, rep i32 | n i32: 32 bytes per cell) | fscan [nf] u64 | vscan [nv] u64 | the scan's
+ * scratch | cell_of [nv] i32.  Nothing beyond that size is touched.
+ *
+ * Every floating-point operation is fp64 and rounded on its own, in the order written (the library
+ * is built with -ffp-contract=off); only + - * /, floor, rint (to nearest, ties to even),
+ * comparisons and conversions occur, so a NumPy restatement gives the same bits
+ * (tests/simplify_truth.py).
+ *
+ * The cell of a vertex p, per axis k:
+ *     t = ((double) p_k - origin_k) / cell_k;  q_k = floor(t);  u_k = t - q_k   (exact)
+ *     w_k = (uint64) rint(u_k * 2097152.0)                                       0 <= w_k <= 2^21
+ * The vertex is BINNED if 0 <= q_k < dims_k on all three axes (which a NaN or infinite t fails),
+ * into cell (q_x dims_y + q_y) dims_z + q_z.  Any other vertex -- NaN, infinite, outside the grid
+ * -- is a SINGLETON: a cluster of its own.
+ *
+ * Per cell, by integer atomics only: rep = the smallest binned vertex index, n = the number of
+ * binned vertices, S_k = the sum of their w_k as u64.  With nv <= 2^31 - 2, S_k < 2^53 and
+ * (double) S_k is exact.
+ *
+ * The position of a cluster: the member's three f32 bits if n == 1 or the cluster is a singleton;
+ * otherwise, per axis,
+ *     x_k = origin_k + cell_k * ((double) q_k + ((double) S_k / (double) n) / 2097152.0)
+ * stored as (float) x_k.
+ *
+ * A face maps each of its indices to the cluster of that vertex, named by rep, or by the vertex
+ * itself for a singleton.  It is KEPT if all three indices lie in [0, nv) and the three clusters
+ * are pairwise different; kept faces keep their order and their winding.  A cluster is USED if a
+ * kept face names it; the used clusters are the output vertices, in ascending order of `source`,
+ * so no output vertex is in no face.
+ *
+ * The result is one fixed set of arrays whatever the launch geometry or the order in which the
+ * hardware ran the threads.  Whatever the face indices and the positions hold, nothing is read or
+ * written out of bounds, and no loop has a trip count that depends on data.
+ *
+ * nv == 0: RN_OK, counts = {0, 0}, no kernel launch.  RN_ERR_INVALID, rn_last_error naming the
+ * entry, no launch, outputs untouched: nv or nf negative, nv > 2^31 - 2, 3 nf > 2^31 - 1, a dims_k
+ * < 1, dims_x dims_y dims_z > 2^31 - 1, a cell_k not finite or <= 0, an origin_k not finite, a NULL
+ * origin / cell / dims / counts, and with nv > 0 a NULL vertices_in / vertices_out / workspace, a
+ * NULL faces_in / faces_out with nf > 0, a workspace that is not 8-byte aligned, vertices_out ==
+ * vertices_in, faces_out == faces_in, either output equal to workspace. */
+int64_t rn_mesh_simplify_workspace_bytes(int64_t nv, int64_t nf, const int32_t dims[3]);
+int rn_mesh_simplify(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t nf,
+                     const int32_t *faces_in, const double origin[3], const double cell[3],
+                     const int32_t dims[3],
+                     float *vertices_out, int32_t *faces_out, int32_t *source, int32_t *cluster,
+                     int64_t *counts, void *workspace, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -51,6 +51,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_components.inl"),
             os.path.join(CSRC, "raynet_components_args.h"),
             os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
+            os.path.join(CSRC, "raynet_simplify.inl"),
+            os.path.join(CSRC, "raynet_simplify_args.h"),
             HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
@@ -222,6 +224,8 @@ SIGNATURES = {
     "rn_mesh_components": [_P, _L, _L, _P, _P, _P, _P, _P, _P],
     "rn_mesh_smooth_workspace_bytes": [_P, _L, _L],
     "rn_mesh_smooth": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],
+    "rn_mesh_simplify_workspace_bytes": [_L, _L, _P],
+    "rn_mesh_simplify": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],
@@ -259,5 +263,6 @@ def load():
     lib.rn_slab_boxes_size.restype = ctypes.c_int64
     lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
+    lib.rn_mesh_simplify_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib

@@ -1247,5 +1247,9 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // Taubin smoothing of a surface mesh: a gather over the corner table
 #include "raynet_smooth.inl"
 
+// vertex clustering of a surface mesh on a uniform grid: integer atomics and the scan below
+// 
+#include "raynet_simplify.inl"
+
 // the surface of a belief grid: marching tetrahedra and the grid-level scan
 #include "raynet_isosurface.inl"

@@ -54,6 +54,21 @@ def _chk(t, dtype, min_numel=0, name="tensor", optional=False, align=4):
     return t
 
 
+def _three_ints(x, name):
+    """Three whole numbers of a host array argument (dims), each an int32."""
+    a = np.asarray(x)
+    if a.shape != (3,) or not np.all(a == np.floor(a)) or np.any(np.abs(a) >= 2 ** 31):
+        raise ValueError("%s: three whole numbers, got %r" % (name, x))
+    return [int(v) for v in a]
+
+
+def _three_floats(x, name):
+    a = np.asarray(x, np.float64)
+    if a.shape != (3,):
+        raise ValueError("%s: three numbers, got %r" % (name, x))
+    return [float(v) for v in a]
+
+
 SCATTER_ITEM_TILES = 1 << 19      # tiles an int32 item `tile << 12 | ...` can name
 
 
@@ -470,6 +485,47 @@ class HipContext(object):
             int(iterations), float(lam), float(mu), float(max_move), _ptr(workspace), _ptr(out),
             _stream()))
         return out
+
+    # ---- vertex clustering of a mesh (raynet_amd/simplify.py) ----------------------------------
+    def mesh_simplify_workspace_bytes(self, nv, nf, dims):
+        """rn_mesh_simplify_workspace_bytes: the bytes rn_mesh_simplify needs for nv vertices, nf
+        faces and a grid of dims[0] x dims[1] x dims[2] cells (32 bytes per cell)."""
+        d = (ctypes.c_int32 * 3)(*_three_ints(dims, "dims"))
+        n = int(self.lib.rn_mesh_simplify_workspace_bytes(int(nv), int(nf), d))
+        if n < 0:
+            raise ValueError("rn_mesh_simplify_workspace_bytes: bad sizes (nv %d, nf %d, dims %s)"
+                             % (nv, nf, tuple(d)))
+        return n
+
+    def mesh_simplify(self, vertices, faces, origin, cell, dims, workspace=None):
+        """rn_mesh_simplify: vertices (nv, 3) f32, faces (nf, 3) i32, the grid (origin [3], cell
+        [3] > 0, dims [3] >= 1 on the host) -> (vertices_out (nv', 3) f32, faces_out (nf', 3) i32,
+        source [nv'] i32, cluster [nv] i32): the vertices that share a cell become one at their
+        mean, faces with two corners in one cluster and vertices no face is left for vanish.
+        workspace: a uint8 tensor of at least mesh_simplify_workspace_bytes(nv, nf, dims) bytes,
+        8-byte aligned (allocated if None).  Synchronises the stream once: the two counts come
+        back to slice the outputs."""
+        nv, nf = len(vertices), len(faces)
+        _chk(vertices, torch.float32, 3 * nv, "vertices")
+        _chk(faces, torch.int32, 3 * nf, "faces")
+        d = (ctypes.c_int32 * 3)(*_three_ints(dims, "dims"))
+        o = (ctypes.c_double * 3)(*_three_floats(origin, "origin"))
+        c = (ctypes.c_double * 3)(*_three_floats(cell, "cell"))
+        need = self.mesh_simplify_workspace_bytes(nv, nf, dims)
+        if workspace is None:
+            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
+        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        device = vertices.device
+        vertices_out = torch.empty((nv, 3), dtype=torch.float32, device=device)
+        faces_out = torch.empty((nf, 3), dtype=torch.int32, device=device)
+        source = torch.empty((nv,), dtype=torch.int32, device=device)
+        cluster = torch.empty((nv,), dtype=torch.int32, device=device)
+        counts = torch.empty((2,), dtype=torch.int64, device=device)
+        self._check(self.lib.rn_mesh_simplify(
+            self._h, nv, _ptr(vertices), nf, _ptr(faces), o, c, d, _ptr(vertices_out),
+            _ptr(faces_out), _ptr(source), _ptr(cluster), _ptr(counts), _ptr(workspace), _stream()))
+        nv_out, nf_out = (int(x) for x in counts.tolist())
+        return vertices_out[:nv_out], faces_out[:nf_out], source[:nv_out], cluster
 
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):

@@ -32,6 +32,10 @@ observation ends.
                      drop the floaters first: the connected components of the mesh with fewer than
                      N faces, with fewer than X times the largest one's faces, all but the K
                      largest (raynet_amd.components; before normals, colours and --mesh_cloud)
+--simplify X [--simplify_keep_duplicates]
+                     then simplify the surface: the vertices that share a cell of X voxel sides
+                     become one vertex at their mean, duplicate faces dropped
+                     (raynet_amd.simplify; before --smooth, normals, colours and --mesh_cloud)
 --smooth N [--smooth_lambda L --smooth_mu M --smooth_max_move X --smooth_free_boundary]
                      then smooth the surface: N Taubin iterations, no coordinate moved farther than
                      X sides of the smallest voxel (default 1), the border of the mesh pinned
@@ -43,7 +47,7 @@ import sys
 
 import numpy as np
 
-from . import component_flags, smooth_flags
+from . import component_flags, simplify_flags, smooth_flags
 from .convert_to_pointcloud import find_format
 
 
@@ -81,6 +85,7 @@ def build_parser():
                    help="--mesh_cloud: how many area-weighted points to draw")
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
     component_flags.add_arguments(p)
+    simplify_flags.add_arguments(p)
     smooth_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.render_volume
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
@@ -118,6 +123,7 @@ def main(argv=None):
     if args.gt and args.confidence_weights:
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
     component_flags.check(parser, args)
+    simplify_flags.check(parser, args)
     smooth_flags.check(parser, args)
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
@@ -162,6 +168,7 @@ def main(argv=None):
     mesh = component_flags.apply(volume.mesh(args.min_weight), args)
     bbox = volume.bbox.astype(np.float64)
     voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
+    mesh = simplify_flags.apply(mesh, args, voxel, bbox[:3])
     mesh = smooth_flags.apply(mesh, args, voxel)
     if (args.normals or args.color or args.mesh_cloud) and mesh.empty:
         parser.error("the fused surface is empty: no voxel pair straddles a measured depth")

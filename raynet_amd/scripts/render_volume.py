@@ -36,6 +36,10 @@ floaters first -- the connected components of the mesh with fewer than N faces, 
 times the largest one's faces, all but the K largest (raynet_amd.components) -- before colours and
 --mesh_cloud.
 
+--simplify X [--simplify_keep_duplicates], with --mesh: then simplify the surface -- the vertices
+that share a cell of X voxel sides become one vertex at their mean, duplicate faces dropped
+(raynet_amd.simplify) -- before --smooth, colours and --mesh_cloud.
+
 --smooth N [--smooth_lambda L --smooth_mu M --smooth_max_move X --smooth_free_boundary], with
 --mesh: then smooth the surface -- N Taubin iterations, no coordinate moved farther than X sides of
 the smallest voxel (default 1), the border of an --open mesh pinned (raynet_amd.smoothing) --
@@ -47,7 +51,7 @@ import sys
 
 import numpy as np
 
-from . import component_flags, smooth_flags
+from . import component_flags, simplify_flags, smooth_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -84,6 +88,7 @@ def build_parser():
     p.add_argument("--depth_tolerance", type=float, default=1.0,
                    help="--color: the slack of the occlusion test, in voxel diagonals")
     component_flags.add_arguments(p)
+    simplify_flags.add_arguments(p)
     smooth_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
@@ -117,6 +122,10 @@ def main(argv=None):
     if component_flags.given(args) and not args.mesh:
         parser.error("--%s goes with --mesh PATH: the components are the mesh's"
                      % component_flags.given(args)[0])
+    simplify_flags.check(parser, args)
+    if simplify_flags.given(args) and not args.mesh:
+        parser.error("--%s goes with --mesh PATH: the simplification is the mesh's"
+                     % simplify_flags.given(args)[0])
     smooth_flags.check(parser, args)
     if smooth_flags.given(args) and not args.mesh:
         parser.error("--%s goes with --mesh PATH: the smoothing is the mesh's"
@@ -151,6 +160,7 @@ def main(argv=None):
         mesh = component_flags.apply(volume.mesh(args.threshold, closed=not args.open), args)
         bbox = volume.bbox.astype(np.float64)
         voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
+        mesh = simplify_flags.apply(mesh, args, voxel, bbox[:3])
         mesh = smooth_flags.apply(mesh, args, voxel)
         if args.mesh and args.color:
             if mesh.empty or not frames:

@@ -137,6 +137,27 @@ class SurfaceMesh(object):
         from . import components
         return components.filter_small(self, min_faces, min_fraction, keep_largest)[0]
 
+    # ---- simplification (simplify.py) ---------------------------------
+    def simplified(self, cell, origin=None, drop_duplicate_faces=True):
+        """-> a new SurfaceMesh with the vertices of every cell of a uniform grid (sides `cell`, a
+        number or one per axis; simplify.simplify_mesh: the keywords are its own) merged at their
+        mean, without the faces and vertices that vanish that way.  Colours are those of each
+        cluster's smallest vertex, normals are recomputed if and only if this mesh has them.  An
+        empty mesh gives an empty mesh, without the GPU."""
+        from . import simplify
+        if self.empty:
+            simplify.cluster_grid(self.vertices, cell, origin)
+            return SurfaceMesh(self.vertices.copy(), self.faces.copy(), self.normals, self.colors)
+        vertices, faces, source = simplify.simplify_mesh(self.vertices, self.faces, cell, origin,
+                                                         drop_duplicate_faces)
+        out = SurfaceMesh(vertices, faces, None,
+                          None if self.colors is None else self.colors[source])
+        if self.normals is not None and out.empty:      # (everything in one cell)
+            out.normals = np.zeros_like(out.vertices)
+        elif self.normals is not None:
+            out.compute_normals()
+        return out
+
     # ---- smoothing (smoothing.py, DESIGN.md section 23) -------------------------------------
     def smoothed(self, iterations=10, lam=0.5, mu=-0.53, fixed="boundary", max_move=None):
         """-> a new SurfaceMesh with the vertices after `iterations` Taubin iterations
