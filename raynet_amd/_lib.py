@@ -53,6 +53,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
             os.path.join(CSRC, "raynet_simplify.inl"),
             os.path.join(CSRC, "raynet_simplify_args.h"),
+            os.path.join(CSRC, "raynet_mesh_args.h"),
+            os.path.join(CSRC, "raynet_scan.inl"), os.path.join(CSRC, "raynet_scan_args.h"),
             HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:

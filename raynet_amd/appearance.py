@@ -31,17 +31,32 @@ class ProjectedColors(object):
         return self.views != 0
 
 
-def _context():
+def _context(work="colours"):
     if not torch.cuda.is_available():
         raise _lib.RaynetHipError(
-            "no GPU visible: raynet_amd colours on MI355X only (no CPU fallback)")
+            "no GPU visible: raynet_amd %s on MI355X only (no CPU fallback)" % work)
     from .hip_implementations import get_context
     return get_context()
 
 
+def _tensor(x):
+    return x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+
+
 def _dev(x, dtype, device):
-    t = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device=device, dtype=dtype).contiguous()
+    return _tensor(x).to(device=device, dtype=dtype).contiguous()
+
+
+def faces_tensor(faces):
+    """faces (nf, 3) of vertex indices, a tensor on any device or an array -> an (nf, 3) tensor on
+    the faces' device, with their dtype."""
+    return _tensor(faces).reshape(-1, 3)
+
+
+def check_face_indices(faces, n_vertices):
+    """ValueError for faces (tensor or array) with an index outside the n_vertices vertices."""
+    if len(faces) and (int(faces.min()) < 0 or int(faces.max()) >= n_vertices):
+        raise ValueError("faces: a vertex index outside 0..%d" % (n_vertices - 1))
 
 
 def corner_table(faces, n_vertices):
@@ -81,8 +96,7 @@ def vertex_normals(vertices, faces, unit=True):
     ctx = _context()
     v = _dev(vertices, torch.float32, ctx.device).reshape(-1, 3)
     f = _dev(faces, torch.int32, ctx.device).reshape(-1, 3)
-    if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
-        raise ValueError("faces: a vertex index outside 0..%d" % (len(v) - 1))
+    check_face_indices(f, len(v))
     offsets, corners = corner_table(f, len(v))
     normals = ctx.vertex_area_normals(v, f, offsets, corners).cpu().numpy()
     return normalized(normals) if unit else normals

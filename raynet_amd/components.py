@@ -15,7 +15,7 @@ There is no CPU route: without a GPU `mesh_components` raises RaynetHipError.
 import numpy as np
 import torch
 
-from . import _lib
+from .appearance import _context, _dev
 
 
 class MeshComponents(object):
@@ -101,16 +101,10 @@ def mesh_components(faces, n_vertices):
     """faces (nf, 3) of vertex indices (array or tensor, host or device) of a mesh with
     `n_vertices` vertices -> MeshComponents.  A face with an index outside [0, n_vertices)
     connects nothing and is counted nowhere."""
-    if not torch.cuda.is_available():
-        raise _lib.RaynetHipError(
-            "no GPU visible: raynet_amd labels components on MI355X only (no CPU fallback)")
-    from .hip_implementations import get_context
-    ctx = get_context()
-    t = faces.detach() if isinstance(faces, torch.Tensor) else \
-        torch.from_numpy(np.ascontiguousarray(faces))
-    t = t.to(device=ctx.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    ctx = _context("labels components")
+    f = _dev(faces, torch.int32, ctx.device).reshape(-1, 3)
     with torch.cuda.device(ctx.device):
-        labels, vertex_counts, face_counts = ctx.mesh_components(t, int(n_vertices))
+        labels, vertex_counts, face_counts = ctx.mesh_components(f, int(n_vertices))
     return MeshComponents(labels.cpu().numpy(), vertex_counts.cpu().numpy(),
                           face_counts.cpu().numpy())
 

@@ -2,30 +2,32 @@
 // rn_vertex_area_normals / rn_project_colors (raynet_appearance.inl), host-only and free of HIP so
 // that they compile into a stand-alone program (tests/appearance_args_main.cpp, built with the
 // address and undefined-behaviour sanitizers by tests/test_appearance_cpu.py).  The launchers act
-// on the verdicts; the kernels guard and address their reads with the constexpr functions below.
+// on the verdicts; the kernels guard and address their reads with the constexpr functions below
+// and with the mesh guards of raynet_mesh_args.h.
 #pragma once
 
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
+#include "raynet_mesh_args.h"
+
 namespace rn_app {
+
+using rn_mesh::Verdict, rn_mesh::INVALID, rn_mesh::EMPTY, rn_mesh::LAUNCH;
+using rn_mesh::INT32_LIMIT, rn_mesh::sizes_ok;
+using rn_mesh::vertex_in, rn_mesh::corner_in, rn_mesh::clamp_slot, rn_mesh::xyz_index;
 
 constexpr int MAX_VIEWS = 32;           // one bit of the `views` word each
 constexpr int MAX_CHANNELS = 4;
 constexpr int CAMERA_DOUBLES = 15;      // P [3][4] row-major | centre [3]
-constexpr int64_t INT32_LIMIT = ((int64_t)1 << 31) - 1;
-
-enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
 
 // rn_vertex_area_normals.  The scalars first, then nv == 0 (nothing to write: EMPTY, whatever the
 // pointers), then the pointers: faces and corners are read only where there are faces.
 inline Verdict normals_args(bool have_ctx, int64_t nv, const void *vertices, int64_t nf,
                             const void *faces, const void *offsets, const void *corners,
                             const void *normals) {
-    if (!have_ctx || nv < 0 || nf < 0) return INVALID;
-    if (nv > INT32_LIMIT - 1) return INVALID;       // offsets has nv + 1 entries, indices are int32
-    if (nf > INT32_LIMIT / 3) return INVALID;       // a corner 3 f + slot is an int32
+    if (!have_ctx || !sizes_ok(nv, nf)) return INVALID;
     if (nv == 0) return EMPTY;
     if (!vertices || !offsets || !normals) return INVALID;
     if (nf > 0 && (!faces || !corners)) return INVALID;
@@ -54,14 +56,8 @@ inline Verdict colors_args(bool have_ctx, int64_t n, const void *points, int32_t
     return LAUNCH;
 }
 
-// ---- what the kernels guard and address with (constexpr: the same functions on the device) ----
-// the corner c = 3 f + slot names an entry of `faces`
-constexpr bool corner_in(int64_t c, int64_t nf) { return c >= 0 && c < 3 * nf; }
-constexpr bool vertex_in(int64_t v, int64_t nv) { return v >= 0 && v < nv; }
-// the range [first, last) of a vertex's corners, cut to the entries `corners` has
-constexpr int64_t clamp_slot(int64_t k, int64_t nf) { return k < 0 ? 0 : (k > 3 * nf ? 3 * nf : k); }
-constexpr size_t xyz_index(int64_t row, int column) { return 3 * (size_t)row + (size_t)column; }
-
+// ---- what the kernels guard and address with (constexpr: the same functions on the device):
+// rn_mesh's for the mesh, and for the images ----
 // pixel (view, y, x) of a [V][H][W] map, channel c of a [V][H][W][C] image
 constexpr size_t depth_index(int v, int y, int x, int H, int W) {
     return ((size_t)v * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;

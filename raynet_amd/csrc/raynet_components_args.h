@@ -3,7 +3,8 @@
 // a stand-alone program (tests/components_args_main.cpp, built with the address and
 // undefined-behaviour sanitizers and once more with the thread sanitizer by
 // tests/test_components_cpu.py).  The launcher acts on the verdict; the kernels decide which faces
-// count, size their grids and unite / find with the functions below.
+// count, size their grids and unite / find with the functions below and the guards of
+// raynet_mesh_args.h.
 //
 // The union-find is a template over an atomics policy A with
 //     int32_t A::load(int32_t x) const                          parent[x], a relaxed atomic load
@@ -27,39 +28,32 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "raynet_mesh_args.h"
+
 namespace rn_cc {
 
-constexpr int64_t INT32_LIMIT = ((int64_t)1 << 31) - 1;
-constexpr int MAX_BLOCKS = 2048;        // the rest of a launch is a grid-stride loop
-
-enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
+using rn_mesh::Verdict, rn_mesh::INVALID, rn_mesh::EMPTY, rn_mesh::LAUNCH;
+using rn_mesh::INT32_LIMIT, rn_mesh::MAX_BLOCKS, rn_mesh::sizes_ok, rn_mesh::blocks;
+using rn_mesh::vertex_in, rn_mesh::xyz_index;
 
 // rn_mesh_components.  The scalars first, then nv == 0 (nothing to write: EMPTY, whatever the
 // pointers), then the pointers: faces is read only where there are faces; the counts and the
 // status word are optional.
 inline Verdict components_args(bool have_ctx, int64_t nv, int64_t nf, const void *faces,
                                const void *labels) {
-    if (!have_ctx || nv < 0 || nf < 0) return INVALID;
-    if (nv > INT32_LIMIT - 1) return INVALID;       // a vertex and the bound nv + 1 are int32
-    if (nf > INT32_LIMIT / 3) return INVALID;       // an entry 3 f + slot of `faces` is an int32
+    if (!have_ctx || !sizes_ok(nv, nf)) return INVALID;
     if (nv == 0) return EMPTY;
     if (!labels) return INVALID;
     if (nf > 0 && !faces) return INVALID;
     return LAUNCH;
 }
 
-// ---- what the kernels guard, address and size their grids with ----
-constexpr bool vertex_in(int64_t v, int64_t nv) { return v >= 0 && v < nv; }
+// ---- what the kernels guard, address and size their grids with: rn_mesh's, and ----
 // a face counts (connects its vertices, is counted) iff all three indices name vertices
 constexpr bool face_counts_in(int64_t nv, int64_t a, int64_t b, int64_t c) {
-    return vertex_in(a, nv) && vertex_in(b, nv) && vertex_in(c, nv);
+    return rn_mesh::face_names_vertices(nv, a, b, c);
 }
-constexpr size_t face_index(int64_t f, int slot) { return 3 * (size_t)f + (size_t)slot; }
-// blocks of `block` threads over n items, at most MAX_BLOCKS (and at least one)
-constexpr int64_t blocks(int64_t n, int block) {
-    const int64_t want = (n + block - 1) / block;
-    return want < 1 ? 1 : (want > MAX_BLOCKS ? MAX_BLOCKS : want);
-}
+constexpr size_t face_index(int64_t f, int slot) { return xyz_index(f, slot); }
 // the hard bound of every chase and every retry loop
 constexpr int64_t step_bound(int64_t nv) { return nv + 1; }
 

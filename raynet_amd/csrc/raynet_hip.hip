@@ -1247,9 +1247,12 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // Taubin smoothing of a surface mesh: a gather over the corner table
 #include "raynet_smooth.inl"
 
-// vertex clustering of a surface mesh on a uniform grid: integer atomics and the scan below
-// 
+// the grid-level exclusive scan of 64-bit words, in front of its two users
+#include "raynet_scan.inl"
+
+// vertex clustering of a surface mesh on a uniform grid: integer atomics and the scan (DESIGN.md
+// section 24)
 #include "raynet_simplify.inl"
 
-// the surface of a belief grid: marching tetrahedra and the grid-level scan
+// the surface of a belief grid: marching tetrahedra and the scan
 #include "raynet_isosurface.inl"

@@ -5,11 +5,8 @@
 //   k_iso_classify  one thread per lattice point: the eight values of its cell (0 outside the
 //                   grid), the 7-bit mask of its edges (p, d) that carry a vertex and the
 //                   triangles of its cell, as one count word (vertices << 32 | triangles).
-//   k_scan_reduce / k_scan_tile
-//                   the grid-level exclusive scan of 64-bit words: a sum per workgroup, the scan
-//                   of the sums (the same two kernels, one level up, as often as the size asks),
-//                   then every workgroup scans its tile from its own sum.  Separate launches: no
-//                   workgroup waits for another.  scan_exclusive_u64 is the library's helper.
+//   scan_exclusive_u64
+//                   the library's grid-level exclusive scan of the count words (raynet_scan.inl).
 //   k_iso_emit      one thread per lattice point: its vertices at its vertex offset, its cell's
 //                   triangles at its triangle offset; the vertex of an edge is found at
 //                   offset[q] + popcount(mask[q] & ((1 << (d - 1)) - 1)).
@@ -21,8 +18,6 @@
 #include "raynet_isosurface_args.h"
 
 namespace {
-
-static_assert(rn_iso::SCAN_TILE == BLOCK, "one entry of the scan per thread of a workgroup");
 
 // The triangles of a tetrahedron: [tetrahedron][inside pattern of its four corners], derived and
 // checked by tools/isosurface_table.py.  Bits 0-1: how many; 3 bits per entry, triangle 0 from
@@ -116,82 +111,6 @@ __global__ __launch_bounds__(BLOCK) void k_iso_classify(IsoGeom g, const float *
     const unsigned mask = cell.edge_mask();
     counts[p] = rn_iso::pack_counts((uint32_t)__popc(mask), cell.triangles());
     masks[p] = (uint8_t)mask;
-}
-
-// ------------------------------------------------------------------ the grid-level scan
-// inclusive sum over the 64 lanes of a wavefront
-__device__ __forceinline__ uint64_t scan_wave_u64(uint64_t x) {
-    const int lane = threadIdx.x & (WAVE - 1);
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, off);
-        x += lane >= off ? y : 0;
-    }
-    return x;
-}
-
-// exclusive sum over the BLOCK threads of a workgroup; *total: the sum of all of them
-__device__ __forceinline__ uint64_t scan_block_u64(uint64_t x, uint64_t *total) {
-    __shared__ uint64_t wave_sum[WAVES_PER_BLOCK];
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const uint64_t incl = scan_wave_u64(x);
-    if (lane == WAVE - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-        const uint64_t s = wave_sum[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    *total = all;
-    return before + (incl - x);
-}
-
-// sums[b] = the sum of tile b of data[0..n)
-__global__ __launch_bounds__(BLOCK) void k_scan_reduce(const uint64_t *__restrict__ data, int64_t n,
-                                                       uint64_t *sums) {
-    const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    uint64_t total;
-    scan_block_u64(i < n ? data[i] : 0, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// data[i] <- offsets[tile of i] + the sum of the entries of its tile in front of i.  offsets:
-// the scanned sums of k_scan_reduce, or null for a single tile; total_out (single tile only,
-// may be null): the sum of everything.
-__global__ __launch_bounds__(BLOCK) void k_scan_tile(uint64_t *data, int64_t n,
-                                                     const uint64_t *__restrict__ offsets,
-                                                     uint64_t *total_out) {
-    const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    uint64_t total;
-    const uint64_t excl = scan_block_u64(i < n ? data[i] : 0, &total);
-    const uint64_t base = offsets ? offsets[blockIdx.x] : 0;
-    if (i < n) data[i] = base + excl;
-    if (total_out && threadIdx.x == 0) *total_out = base + total;
-}
-
-// The exclusive scan of data[0..n) in place, n >= 1; scratch: rn_iso::scan_scratch_words(n)
-// words; total_out (device): the sum of all entries.  Sums wrap modulo 2^64.  Launches only:
-// 2 * scan_levels(n) - 1 of them on `stream`, nothing is synchronised.
-int scan_exclusive_u64(rn_ctx *ctx, uint64_t *data, int64_t n, uint64_t *scratch,
-                       uint64_t *total_out, hipStream_t stream) {
-    if (n <= rn_iso::SCAN_TILE) {
-        hipLaunchKernelGGL(k_scan_tile, dim3(1), dim3(BLOCK), 0, stream, data, n,
-                           (const uint64_t *)nullptr, total_out);
-        RN_LAUNCH_CHECK(ctx);
-        return RN_OK;
-    }
-    const int64_t tiles = rn_iso::scan_tiles(n);
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)tiles), dim3(BLOCK), 0, stream,
-                       (const uint64_t *)data, n, scratch);
-    RN_LAUNCH_CHECK(ctx);
-    const int rc = scan_exclusive_u64(ctx, scratch, tiles, scratch + tiles, total_out, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_scan_tile, dim3((unsigned)tiles), dim3(BLOCK), 0, stream, data, n,
-                       (const uint64_t *)scratch, (uint64_t *)nullptr);
-    RN_LAUNCH_CHECK(ctx);
-    return RN_OK;
 }
 
 // --------------------------------------------------------------------------- the mesh
@@ -323,7 +242,7 @@ int rn_isosurface_count(rn_ctx *ctx, const float *belief, float iso, int32_t clo
     uint64_t *scratch = reinterpret_cast<uint64_t *>(ws + rn_iso::ws_scratch(l));
     uint64_t *total = reinterpret_cast<uint64_t *>(ws + rn_iso::ws_total(l));
     uint8_t *masks = reinterpret_cast<uint8_t *>(ws + rn_iso::ws_masks(l));
-    const dim3 grid((unsigned)rn_iso::scan_tiles(l.points));
+    const dim3 grid((unsigned)rn_scan::scan_tiles(l.points));
     hipLaunchKernelGGL(k_iso_classify, grid, dim3(BLOCK), 0, S(stream), iso_geom(ctx, l, closed),
                        belief, iso, counts, masks);
     RN_LAUNCH_CHECK(ctx);
@@ -358,7 +277,7 @@ int rn_isosurface_emit(rn_ctx *ctx, const float *belief, float iso, int32_t clos
     const float hx = (p.bbox[3] - p.bbox[0]) / (float)p.gx,
                 hy = (p.bbox[4] - p.bbox[1]) / (float)p.gy,
                 hz = (p.bbox[5] - p.bbox[2]) / (float)p.gz;
-    const dim3 grid((unsigned)rn_iso::scan_tiles(l.points));
+    const dim3 grid((unsigned)rn_scan::scan_tiles(l.points));
     hipLaunchKernelGGL(k_iso_emit, grid, dim3(BLOCK), 0, S(stream), iso_geom(ctx, l, closed),
                        belief, iso, (const float *)ctx->axes, hx, hy, hz, offsets, masks, nv, nf,
                        vertices_out, faces_out);

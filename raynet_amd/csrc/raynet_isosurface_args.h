@@ -1,18 +1,20 @@
 // raynet_isosurface_args.h -- the size arithmetic and the argument checks of rn_isosurface_count /
-// rn_isosurface_emit and of the grid-level scan (raynet_isosurface.inl), host-only and free of HIP
-// so that they compile into a stand-alone program (tests/isosurface_args_main.cpp, built with the
-// address and undefined-behaviour sanitizers by tests/test_isosurface_cpu.py).  The launchers act
-// on the verdicts and lay the workspace out with these functions; the kernels guard their output
-// rows with row_in().
+// rn_isosurface_emit (raynet_isosurface.inl), host-only and free of HIP so that they compile into a
+// stand-alone program (tests/isosurface_args_main.cpp, built with the address and
+// undefined-behaviour sanitizers by tests/test_isosurface_cpu.py, which also checks the scan's
+// arithmetic, raynet_scan_args.h's).  The launchers act on the verdicts and lay the workspace out
+// with these functions; the kernels guard their output rows with row_in().
 #pragma once
 
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
+#include "raynet_scan_args.h"
+
 namespace rn_iso {
 
-constexpr int SCAN_TILE = 256;          // entries one workgroup of the scan takes: one per thread
+using rn_scan::scan_levels, rn_scan::scan_scratch_words;
 
 enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
 
@@ -38,28 +40,6 @@ constexpr bool lattice_fits(const Lattice &l) {
 }
 constexpr int64_t max_vertices(const Lattice &l) { return l.cells > 0 ? 7 * l.points : 0; }
 constexpr int64_t max_faces(const Lattice &l) { return 12 * l.cells; }
-
-// ---- the grid-level exclusive scan of n 64-bit words ----
-// Level 0 is the data; level k + 1 holds one sum per SCAN_TILE entries of level k, down to a
-// level of at most SCAN_TILE entries that one workgroup scans on its own.
-constexpr int64_t scan_tiles(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
-// 64-bit words of scratch below the data: every level above level 0
-constexpr int64_t scan_scratch_words(int64_t n) {
-    int64_t words = 0;
-    while (n > SCAN_TILE) {
-        n = scan_tiles(n);
-        words += n;
-    }
-    return words;
-}
-constexpr int scan_levels(int64_t n) {
-    int levels = 1;
-    while (n > SCAN_TILE) {
-        n = scan_tiles(n);
-        levels++;
-    }
-    return levels;
-}
 
 // ---- the workspace: 64-bit words first, the bytes of the edge masks behind them ----
 //   counts  [L]        u64   (vertices << 32 | triangles) per point, then their exclusive scan

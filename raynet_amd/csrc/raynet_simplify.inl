@@ -1,7 +1,6 @@
 // raynet_simplify.inl -- vertex clustering of an indexed triangle mesh on a uniform grid (DESIGN.md
 // section 24; the definition is in include/raynet_hip.h at rn_mesh_simplify).  Included at the end
-// of raynet_hip.hip, in front of raynet_isosurface.inl, whose grid-level scan it uses: declared
-// here, defined there.
+// of raynet_hip.hip, behind the library's scan (raynet_scan.inl).
 //
 //   k_simplify_clear          one thread per cell: the three sums and the count zeroed, rep at its
 //                             largest value.
@@ -12,7 +11,8 @@
 //   k_simplify_face_flags     one thread per face: the kept flag into the scan array, and 1 at the
 //                             smallest vertex of each of its three clusters (plain stores of the
 //                             same value: the race is benign).
-//   scan_exclusive_u64        over the faces, then over the vertices; the totals are `counts`.
+//   scan_exclusive_u64        (raynet_scan.inl) over the faces, then over the vertices; the totals
+//                             are `counts`.
 //   k_simplify_emit_vertices  one thread per vertex: cluster[v]; the smallest vertex of a used
 //                             cluster writes the cluster's row of vertices_out and source.
 //   k_simplify_emit_faces     one thread per face: a kept face's row of faces_out.
@@ -25,10 +25,6 @@
 #include "raynet_simplify_args.h"
 
 namespace {
-
-// raynet_isosurface.inl: the exclusive scan of data[0..n) in place, its total into total_out
-int scan_exclusive_u64(rn_ctx *ctx, uint64_t *data, int64_t n, uint64_t *scratch,
-                       uint64_t *total_out, hipStream_t stream);
 
 struct SimplifyArgs {
     rn_sp::Grid grid;

@@ -7,7 +7,9 @@
 // emit_vertex / emit_face and add the index of the thread, the atomics policy and, in the binning,
 // the sums over the lanes of a wavefront that share a cell (the host program bins vertex by vertex
 // with bin_vertex: integer sums, the same words).  The functions are constexpr only so that the
-// device may call them; nothing here is evaluated at compile time.
+// device may call them; nothing here is evaluated at compile time.  The limits of the sizes, the
+// guards of the indices and the launch geometry are raynet_mesh_args.h's, the size of the scan's
+// scratch raynet_scan_args.h's.
 //
 // The definition is in include/raynet_hip.h at rn_mesh_simplify.  Every
 // floating-point operation below is fp64, written as one operation per rounding and in the
@@ -18,23 +20,21 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "raynet_isosurface_args.h"     // rn_iso::scan_scratch_words: the scan is the library's one
+#include "raynet_mesh_args.h"
+#include "raynet_scan_args.h"
 
 namespace rn_sp {
 
-constexpr int64_t INT32_LIMIT = ((int64_t)1 << 31) - 1;
-constexpr int MAX_BLOCKS = 2048;        // the rest of a launch is a grid-stride loop
+using rn_mesh::Verdict, rn_mesh::INVALID, rn_mesh::EMPTY, rn_mesh::LAUNCH;
+using rn_mesh::INT32_LIMIT, rn_mesh::MAX_BLOCKS, rn_mesh::sizes_ok, rn_mesh::blocks;
+using rn_mesh::vertex_in, rn_mesh::face_in, rn_mesh::xyz_index;
+
 constexpr double FIXED_ONE = 2097152.0; // 2^21: the fixed-point unit of a position inside its cell
 constexpr double ROUND_SHIFT = 4503599627370496.0;    // 2^52: x + 2^52 - 2^52 rounds x to a whole number
 constexpr int32_t NO_REP = 2147483647;  // the `rep` of a cell nobody was binned into
 constexpr int64_t CELL_BYTES = 32;      // S [3] u64 | rep i32 | n i32
 
-enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
-
-// ---- the sizes and the grid: what rn_mesh_simplify_workspace_bytes refuses ----
-constexpr bool sizes_ok(int64_t nv, int64_t nf) {
-    return nv >= 0 && nf >= 0 && nv <= INT32_LIMIT - 1 && nf <= INT32_LIMIT / 3;
-}
+// ---- the grid: with the sizes, what rn_mesh_simplify_workspace_bytes refuses ----
 // the number of cells, or -1 for a dims the entry refuses (no product that could overflow)
 constexpr int64_t cell_count(const int32_t *dims) {
     if (!dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return -1;
@@ -48,7 +48,7 @@ constexpr int64_t cell_count(const int32_t *dims) {
 //   table   [cells][4] u64   S_x, S_y, S_z, then rep (low i32) | n (high i32): 32 bytes per cell
 //   fscan   [nf]       u64   the kept flag of every face, then its exclusive scan
 //   vscan   [nv]       u64   1 at the smallest vertex of every used cluster, then its scan
-//   scratch [scan_scratch_words(max(nv, nf))] u64   (the two scans run one after the other)
+//   scratch [rn_scan::scan_scratch_words(max(nv, nf))] u64   (the two scans run one after the other)
 //   cell_of [nv]       i32   the cell of every binned vertex, -1 for a singleton
 constexpr int64_t ws_table(int64_t, int64_t, int64_t) { return 0; }
 constexpr int64_t ws_fscan(int64_t, int64_t, int64_t cells) { return CELL_BYTES * cells; }
@@ -59,7 +59,7 @@ constexpr int64_t ws_scratch(int64_t nv, int64_t nf, int64_t cells) {
     return ws_vscan(nv, nf, cells) + 8 * nv;
 }
 constexpr int64_t ws_cell_of(int64_t nv, int64_t nf, int64_t cells) {
-    return ws_scratch(nv, nf, cells) + 8 * rn_iso::scan_scratch_words(nv > nf ? nv : nf);
+    return ws_scratch(nv, nf, cells) + 8 * rn_scan::scan_scratch_words(nv > nf ? nv : nf);
 }
 constexpr int64_t workspace_bytes(int64_t nv, int64_t nf, const int32_t *dims) {
     const int64_t cells = cell_count(dims);
@@ -90,18 +90,11 @@ inline Verdict simplify_args(bool have_ctx, int64_t nv, const void *vertices_in,
     return LAUNCH;
 }
 
-// ---- what the kernels guard, address and size their grids with ----
-constexpr bool vertex_in(int64_t v, int64_t nv) { return v >= 0 && v < nv; }
-constexpr bool face_in(int64_t f, int64_t nf) { return f >= 0 && f < nf; }
+// ---- what the kernels guard and address the table with (the mesh: rn_mesh's guards) ----
 constexpr bool cell_in(int64_t c, int64_t cells) { return c >= 0 && c < cells; }
-constexpr size_t xyz_index(int64_t row, int column) { return 3 * (size_t)row + (size_t)column; }
 constexpr size_t sum_index(int64_t cell, int axis) { return 4 * (size_t)cell + (size_t)axis; }
 constexpr size_t rep_index(int64_t cell) { return 8 * (size_t)cell + 6; }   // as an i32 array
 constexpr size_t n_index(int64_t cell) { return 8 * (size_t)cell + 7; }
-constexpr int64_t blocks(int64_t n, int block) {
-    const int64_t want = (n + block - 1) / block;
-    return want < 1 ? 1 : (want > MAX_BLOCKS ? MAX_BLOCKS : want);
-}
 
 // the grid as the kernels carry it, by value
 struct Grid {

@@ -4,7 +4,8 @@
 // (tests/smooth_args_main.cpp, built with the address and undefined-behaviour sanitizers by
 // tests/test_smooth_cpu.py).  The launcher acts on the verdict and walks the steps with
 // step_factor / step_source / step_target; the kernels call ring_entry and step_vertex and add
-// nothing of their own beyond the index of the thread.  The functions are constexpr only so that
+// nothing of their own beyond the index of the thread.  The limits of the sizes, the guards of the
+// indices and the launch geometry are raynet_mesh_args.h's.  The functions are constexpr only so that
 // the device may call them; nothing here is evaluated at compile time.
 //
 // The definition is in include/raynet_hip.h at rn_mesh_smooth.  Every
@@ -16,19 +17,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "raynet_mesh_args.h"
+
 namespace rn_sm {
 
-constexpr int64_t INT32_LIMIT = ((int64_t)1 << 31) - 1;
-constexpr int MAX_BLOCKS = 2048;        // the rest of a launch is a grid-stride loop
+using rn_mesh::Verdict, rn_mesh::INVALID, rn_mesh::EMPTY, rn_mesh::LAUNCH;
+using rn_mesh::INT32_LIMIT, rn_mesh::MAX_BLOCKS, rn_mesh::sizes_ok, rn_mesh::blocks;
+using rn_mesh::vertex_in, rn_mesh::corner_in, rn_mesh::clamp_slot, rn_mesh::xyz_index;
+
 constexpr int32_t MAX_ITERATIONS = 10000;
-
-enum Verdict { INVALID = -1, EMPTY = 0, LAUNCH = 1 };
-
-// the sizes alone: what rn_mesh_smooth_workspace_bytes refuses
-constexpr bool sizes_ok(int64_t nv, int64_t nf) {
-    return nv >= 0 && nf >= 0 && nv <= INT32_LIMIT - 1      // offsets has nv + 1 entries
-           && nf <= INT32_LIMIT / 3;                        // a corner 3 f + slot is an int32
-}
 
 // ---- the workspace: ring [3 nf][2] i32 | scratch [nv][3] f32, rounded up to 8 bytes ----
 constexpr int64_t ring_bytes(int64_t nf) { return 24 * nf; }
@@ -77,18 +74,8 @@ constexpr const float *step_source(int64_t i, int64_t L, const float *in, float 
     return i == 1 ? in : step_target(i - 1, L, scratch, out);
 }
 
-// ---- what the kernels guard, address and size their grids with ----
-constexpr bool corner_in(int64_t c, int64_t nf) { return c >= 0 && c < 3 * nf; }
-constexpr bool vertex_in(int64_t v, int64_t nv) { return v >= 0 && v < nv; }
-// the range [first, last) of a vertex's corners, cut to the entries `corners` has
-constexpr int64_t clamp_slot(int64_t k, int64_t nf) { return k < 0 ? 0 : (k > 3 * nf ? 3 * nf : k); }
-constexpr size_t xyz_index(int64_t row, int column) { return 3 * (size_t)row + (size_t)column; }
+// ---- what the kernels address the ring with (the mesh: rn_mesh's guards) ----
 constexpr size_t ring_index(int64_t k, int which) { return 2 * (size_t)k + (size_t)which; }
-// blocks of `block` threads over n items, at most MAX_BLOCKS (and at least one)
-constexpr int64_t blocks(int64_t n, int block) {
-    const int64_t want = (n + block - 1) / block;
-    return want < 1 ? 1 : (want > MAX_BLOCKS ? MAX_BLOCKS : want);
-}
 
 // ---- the ring entry of table position k in [0, 3 nf): the two other vertices of the face of
 // corners[k], in the face's order after that corner; (-1, -1) for a corner outside [0, 3 nf) or a

@@ -28,18 +28,10 @@ observation ends.
 --mesh_cloud PATH --mesh_samples N [--seed S]
                      also write N area-weighted points of the surface as a point cloud, the form
                      compute_metrics scores
---min_component_faces N, --min_component_fraction X, --keep_largest K
-                     drop the floaters first: the connected components of the mesh with fewer than
-                     N faces, with fewer than X times the largest one's faces, all but the K
-                     largest (raynet_amd.components; before normals, colours and --mesh_cloud)
---simplify X [--simplify_keep_duplicates]
-                     then simplify the surface: the vertices that share a cell of X voxel sides
-                     become one vertex at their mean, duplicate faces dropped
-                     (raynet_amd.simplify; before --smooth, normals, colours and --mesh_cloud)
---smooth N [--smooth_lambda L --smooth_mu M --smooth_max_move X --smooth_free_boundary]
-                     then smooth the surface: N Taubin iterations, no coordinate moved farther than
-                     X sides of the smallest voxel (default 1), the border of the mesh pinned
-                     (raynet_amd.smoothing; before normals, colours and --mesh_cloud)
+the mesh-cleanup flags
+                     drop the floaters (--min_component_faces, --min_component_fraction,
+                     --keep_largest), then --simplify the surface, then --smooth it, before
+                     normals, colours and --mesh_cloud: see raynet_amd.scripts.mesh_flags
 """
 import argparse
 import os
@@ -47,7 +39,7 @@ import sys
 
 import numpy as np
 
-from . import component_flags, simplify_flags, smooth_flags
+from . import mesh_flags
 from .convert_to_pointcloud import find_format
 
 
@@ -84,9 +76,7 @@ def build_parser():
     p.add_argument("--mesh_samples", type=int, default=None,
                    help="--mesh_cloud: how many area-weighted points to draw")
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
-    component_flags.add_arguments(p)
-    simplify_flags.add_arguments(p)
-    smooth_flags.add_arguments(p)
+    mesh_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.render_volume
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -122,9 +112,7 @@ def main(argv=None):
         parser.error("--min_confidence goes with --confidence_weights")
     if args.gt and args.confidence_weights:
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
-    component_flags.check(parser, args)
-    simplify_flags.check(parser, args)
-    smooth_flags.check(parser, args)
+    mesh_flags.check(parser, args)
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
 
@@ -165,17 +153,14 @@ def main(argv=None):
                         weights=weights, border=args.border)
     if args.volume:
         volume.save(args.volume)
-    mesh = component_flags.apply(volume.mesh(args.min_weight), args)
-    bbox = volume.bbox.astype(np.float64)
-    voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
-    mesh = simplify_flags.apply(mesh, args, voxel, bbox[:3])
-    mesh = smooth_flags.apply(mesh, args, voxel)
+    mesh = mesh_flags.apply(volume.mesh(args.min_weight), args, volume)
     if (args.normals or args.color or args.mesh_cloud) and mesh.empty:
         parser.error("the fused surface is empty: no voxel pair straddles a measured depth")
     if args.normals or args.color:
         mesh.compute_normals()
     if args.color:
-        mesh.colorize(scene, frames, tol=float(np.sqrt((voxel ** 2).sum())))
+        mesh.colorize(scene, frames,
+                      tol=float(np.sqrt((mesh_flags.voxel_sides(volume) ** 2).sum())))
     mesh.save_ply(args.output_mesh)
     if args.mesh_cloud:
         mesh.pointcloud(args.mesh_samples, args.seed).save_ply(args.mesh_cloud)

@@ -31,19 +31,9 @@ best.  --depth_tolerance is the slack of the occlusion test in voxel diagonals (
 vertex lies on an edge of a lattice cell, and the surface point its nearest pixel records lies in
 the same or the next cell unless the view is grazing).
 
---min_component_faces N, --min_component_fraction X, --keep_largest K, with --mesh: drop the
-floaters first -- the connected components of the mesh with fewer than N faces, with fewer than X
-times the largest one's faces, all but the K largest (raynet_amd.components) -- before colours and
---mesh_cloud.
-
---simplify X [--simplify_keep_duplicates], with --mesh: then simplify the surface -- the vertices
-that share a cell of X voxel sides become one vertex at their mean, duplicate faces dropped
-(raynet_amd.simplify) -- before --smooth, colours and --mesh_cloud.
-
---smooth N [--smooth_lambda L --smooth_mu M --smooth_max_move X --smooth_free_boundary], with
---mesh: then smooth the surface -- N Taubin iterations, no coordinate moved farther than X sides of
-the smallest voxel (default 1), the border of an --open mesh pinned (raynet_amd.smoothing) --
-before colours and --mesh_cloud.
+The mesh-cleanup flags, with --mesh: drop the floaters (--min_component_faces,
+--min_component_fraction, --keep_largest), then --simplify the surface, then --smooth it, before
+colours and --mesh_cloud: see raynet_amd.scripts.mesh_flags.
 """
 import argparse
 import os
@@ -51,7 +41,7 @@ import sys
 
 import numpy as np
 
-from . import component_flags, simplify_flags, smooth_flags
+from . import mesh_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -87,9 +77,7 @@ def build_parser():
                    help="--color: the weighted mean of the frames that see a vertex, or the best one")
     p.add_argument("--depth_tolerance", type=float, default=1.0,
                    help="--color: the slack of the occlusion test, in voxel diagonals")
-    component_flags.add_arguments(p)
-    simplify_flags.add_arguments(p)
-    smooth_flags.add_arguments(p)
+    mesh_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -118,18 +106,7 @@ def main(argv=None):
         parser.error("--color goes with --mesh PATH: the colours are the mesh's")
     if not (args.depth_tolerance >= 0.0 and args.depth_tolerance < float("inf")):
         parser.error("--depth_tolerance takes a finite number of voxel diagonals, 0 or more")
-    component_flags.check(parser, args)
-    if component_flags.given(args) and not args.mesh:
-        parser.error("--%s goes with --mesh PATH: the components are the mesh's"
-                     % component_flags.given(args)[0])
-    simplify_flags.check(parser, args)
-    if simplify_flags.given(args) and not args.mesh:
-        parser.error("--%s goes with --mesh PATH: the simplification is the mesh's"
-                     % simplify_flags.given(args)[0])
-    smooth_flags.check(parser, args)
-    if smooth_flags.given(args) and not args.mesh:
-        parser.error("--%s goes with --mesh PATH: the smoothing is the mesh's"
-                     % smooth_flags.given(args)[0])
+    mesh_flags.check(parser, args, mesh_requested=bool(args.mesh))
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -157,11 +134,8 @@ def main(argv=None):
     if args.ply:
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
     if args.mesh or args.mesh_cloud:
-        mesh = component_flags.apply(volume.mesh(args.threshold, closed=not args.open), args)
-        bbox = volume.bbox.astype(np.float64)
-        voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
-        mesh = simplify_flags.apply(mesh, args, voxel, bbox[:3])
-        mesh = smooth_flags.apply(mesh, args, voxel)
+        mesh = mesh_flags.apply(volume.mesh(args.threshold, closed=not args.open), args, volume)
+        voxel = mesh_flags.voxel_sides(volume)
         if args.mesh and args.color:
             if mesh.empty or not frames:
                 parser.error("--color: %s" % ("the surface is empty" if mesh.empty else

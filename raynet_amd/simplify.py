@@ -16,7 +16,7 @@ There is no CPU route: without a GPU `simplify_mesh` raises RaynetHipError.
 import numpy as np
 import torch
 
-from .appearance import _context, _dev
+from .appearance import _context, _dev, check_face_indices, faces_tensor
 
 MAX_CELLS = 1 << 28         # 8 GiB of table at the 32 bytes a cell has in the workspace
 CELL_BYTES = 32             # S_x, S_y, S_z u64 | rep i32 | n i32
@@ -63,9 +63,7 @@ def unique_faces(faces):
     vertices, in any order or orientation, and the order of the faces is kept.  Clustering a thin
     sheet maps both of its sides to the same triangles: of a collapsed two-sided sheet only one
     side stays -- the first in the faces' order, with its orientation."""
-    t = faces.detach() if isinstance(faces, torch.Tensor) else \
-        torch.from_numpy(np.ascontiguousarray(faces))
-    f = t.reshape(-1, 3)
+    f = faces_tensor(faces)
     if len(f) == 0:
         return f
     keys = torch.sort(f.to(torch.int64), dim=1).values
@@ -103,8 +101,7 @@ def simplify_mesh(vertices, faces, cell, origin=None, drop_duplicate_faces=True)
         raise ValueError("vertices: at most 2^31 - 2, got %d" % nv)
     if 3 * len(f) > 2 ** 31 - 1:
         raise ValueError("faces: at most (2^31 - 1) / 3, got %d" % len(f))
-    if len(f) and (int(f.min()) < 0 or int(f.max()) >= nv):
-        raise ValueError("faces: a vertex index outside 0..%d" % (nv - 1))
+    check_face_indices(f, nv)
     start, cell3, dims = cluster_grid(v, cell, origin)
     out_v, out_f, source, _ = mesh_simplify(v, f, start, cell3, dims)
     if drop_duplicate_faces and len(out_f):

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .appearance import _context, _dev, corner_table
+from .appearance import _context, _dev, check_face_indices, corner_table, faces_tensor
 
 MAX_ITERATIONS = 10000
 
@@ -28,9 +28,7 @@ def boundary_vertices(faces, n_vertices):
     undirected pair of two different vertices of a face; a face with an index outside [0, nv) has
     no edges."""
     nv = int(n_vertices)
-    t = faces.detach() if isinstance(faces, torch.Tensor) else \
-        torch.from_numpy(np.ascontiguousarray(faces))
-    f = t.reshape(-1, 3).to(torch.int64)
+    f = faces_tensor(faces).to(torch.int64)
     f = f[((f >= 0) & (f < nv)).all(1)]
     a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
     lo, hi = torch.minimum(a, b), torch.maximum(a, b)
@@ -85,8 +83,7 @@ def smooth_vertices(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed="bo
     v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
     nv = len(v)
-    if len(f) and (int(f.min()) < 0 or int(f.max()) >= nv):
-        raise ValueError("faces: a vertex index outside 0..%d" % (nv - 1))
+    check_face_indices(f, nv)
     if fixed is None:
         pinned = None
     elif isinstance(fixed, str):

@@ -15,6 +15,7 @@ GPU, csrc/raynet_isosurface.inl), which the mesh tools of 
 import numpy as np
 import torch
 
+from .appearance import check_face_indices
 from .common.scene import get_voxel_grid
 
 MAX_M = 1024        # rn_create's limit on the steps of a ray
@@ -55,8 +56,7 @@ class SurfaceMesh(object):
             faces = faces.detach().cpu().numpy()
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         faces = np.asarray(faces).reshape(-1, 3)
-        if len(faces) and (faces.min() < 0 or faces.max() >= len(self.vertices)):
-            raise ValueError("faces: a vertex index outside 0..%d" % (len(self.vertices) - 1))
+        check_face_indices(faces, len(self.vertices))
         self.faces = np.ascontiguousarray(faces, dtype=np.int32)
         self.normals = self.colors = None
         if normals is not None:
@@ -85,16 +85,9 @@ class SurfaceMesh(object):
         and without the vertices no remaining face names, renumbered; the order of faces and
         vertices is kept, normals and colours go along.  (The iso-surface of a field with NaN
         entries has such vertices: HipContext.isosurface, fusion.TSDFVolume.mesh.)"""
-        vertices, faces = torch.from_numpy(self.vertices), torch.from_numpy(self.faces).long()
-        finite = torch.isfinite(vertices).all(1)
-        faces = faces[finite[faces].all(1)]
-        used = torch.zeros(len(vertices), dtype=torch.bool)
-        used[faces.reshape(-1)] = True
-        new = torch.cumsum(used, 0) - 1
-        keep = used.numpy()
-        return SurfaceMesh(self.vertices[keep], new[faces].to(torch.int32).numpy(),
-                           None if self.normals is None else self.normals[keep],
-                           None if self.colors is None else self.colors[keep])
+        from . import components
+        finite = np.isfinite(self.vertices).all(1)
+        return components.keep_faces(self, finite[self.faces].all(1))
 
     # ---- connected components (components.py, DESIGN.md section 22) ------------------------
     def components(self):

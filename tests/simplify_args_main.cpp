@@ -137,7 +137,7 @@ static void test_layout() {
     for (auto &d : shapes)
         for (auto &s : sizes) {
             const int64_t nv = s[0], nf = s[1], cells = cell_count(d);
-            const int64_t words = rn_iso::scan_scratch_words(nv > nf ? nv : nf);
+            const int64_t words = rn_scan::scan_scratch_words(nv > nf ? nv : nf);
             const int64_t parts[][2] = {{ws_table(nv, nf, cells), CELL_BYTES * cells},
                                         {ws_fscan(nv, nf, cells), 8 * nf},
                                         {ws_vscan(nv, nf, cells), 8 * nv},

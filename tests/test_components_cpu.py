@@ -243,15 +243,15 @@ def test_an_empty_mesh_stays_empty_without_the_gpu(truth_labels):
 
 
 def test_the_flag_helper_filters_and_reports(truth_labels, capsys):
-    from raynet_amd.scripts import component_flags, fuse_depth_maps
+    from raynet_amd.scripts import fuse_depth_maps, mesh_flags
     from raynet_amd.volume import SurfaceMesh
     vertices, faces, _, _ = _pieces(2)
     mesh = SurfaceMesh(vertices, faces)
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply"])
-    assert component_flags.apply(mesh, args) is mesh and capsys.readouterr().out == ""
+    assert mesh_flags.drop_components(mesh, args) is mesh and capsys.readouterr().out == ""
     assert truth_labels == []
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply", "--min_component_faces", "4"])
-    out = component_flags.apply(mesh, args)
+    out = mesh_flags.drop_components(mesh, args)
     want_v, want_f, _, found, kept = ct.filtered(vertices, faces, min_faces=4)
     assert np.array_equal(out.faces, want_f)
     assert capsys.readouterr().out == "components: %d found, %d kept, %d -> %d faces\n" % (

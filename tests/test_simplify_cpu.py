@@ -50,7 +50,7 @@ def test_the_launcher_and_the_kernels_use_the_header():
     for use in ("rn_sp::workspace_bytes(", "rn_sp::grid_of(", "rn_sp::tables_of(",
                 "rn_sp::ws_scratch(", "rn_sp::blocks("):
         assert use in code, use
-    assert code.count("scan_exclusive_u64(") == 3 and "k_scan" not in code     # declared, called twice
+    assert code.count("scan_exclusive_u64(") == 2 and "k_scan" not in code     # called twice
     kernels = re.findall(r"__global__ __launch_bounds__\(BLOCK\) void (\w+)\(SimplifyArgs a\) \{\n(.*?)\n\}\n",
                          code, re.S)
     calls = {"k_simplify_clear": "rn_sp::clear_cell(", "k_simplify_bin": "rn_sp::place_vertex(",
@@ -324,25 +324,25 @@ def test_unique_faces_by_the_torch_route_is_the_dictionarys():
 
 # ------------------------------------------------------------------------------ the scripts
 def test_the_flag_helper_simplifies_and_reports(truth_call, capsys, tmp_path):
-    from raynet_amd.scripts import fuse_depth_maps, simplify_flags
+    from raynet_amd.scripts import fuse_depth_maps, mesh_flags
     from raynet_amd.volume import SurfaceMesh
     vertices, faces = st.binary_ball()
     mesh = SurfaceMesh(vertices, faces)
     voxel, corner = np.array([0.5, 0.25, 1.0]), np.array([-0.5, -0.5, -0.5])
     # without --simplify: the very object, nothing printed, and so the bytes of the file
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply"])
-    assert simplify_flags.given(args) == []
-    assert simplify_flags.apply(mesh, args, voxel, corner) is mesh and capsys.readouterr().out == ""
+    assert mesh_flags.given(args) == []
+    assert mesh_flags.simplify(mesh, args, voxel, corner) is mesh and capsys.readouterr().out == ""
     assert truth_call == []
     before, after = str(tmp_path / "before.ply"), str(tmp_path / "after.ply")
     mesh.save_ply(before)
-    simplify_flags.apply(mesh, args, voxel, corner).save_ply(after)
+    mesh_flags.simplify(mesh, args, voxel, corner).save_ply(after)
     assert open(before, "rb").read() == open(after, "rb").read()
     # --simplify 2.5: cells of 2.5 voxel sides per axis, anchored at the box's minimum -- whole
     # cells in front of it where the closed surface reaches out of the box
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply", "--simplify", "2.5"])
-    assert simplify_flags.given(args) == ["simplify"]
-    out = simplify_flags.apply(mesh, args, voxel, corner)
+    assert mesh_flags.given(args) == ["simplify"]
+    out = mesh_flags.simplify(mesh, args, voxel, corner)
     call = truth_call[-1]
     assert np.array_equal(call["cell"], 2.5 * voxel)
     steps = (call["origin"] - corner) / call["cell"]
@@ -359,8 +359,8 @@ def test_the_flag_helper_simplifies_and_reports(truth_call, capsys, tmp_path):
     quarter = np.array([0.25, 0.25, 0.25])
     args = fuse_depth_maps.build_parser().parse_args(
         ["s", "p", "o.ply", "--simplify", "2", "--simplify_keep_duplicates"])
-    assert simplify_flags.given(args) == ["simplify", "simplify_keep_duplicates"]
-    out = simplify_flags.apply(sheet, args, quarter, np.zeros(3))
+    assert mesh_flags.given(args) == ["simplify", "simplify_keep_duplicates"]
+    out = mesh_flags.simplify(sheet, args, quarter, np.zeros(3))
     call = truth_call[-1]
     assert np.array_equal(call["cell"], [0.5] * 3) and np.array_equal(call["origin"], [0.0] * 3)
     want = sp.simplify(sheet.vertices, sheet.faces, call["origin"], call["cell"], call["dims"])
@@ -368,7 +368,7 @@ def test_the_flag_helper_simplifies_and_reports(truth_call, capsys, tmp_path):
     assert np.array_equal(out.faces, want[1]) and 0 < len(single) == len(want[1]) // 2
     assert "simplify: cell 2 voxel sides, " in capsys.readouterr().out
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply", "--simplify", "2"])
-    assert np.array_equal(simplify_flags.apply(sheet, args, quarter, np.zeros(3)).faces, single)
+    assert np.array_equal(mesh_flags.simplify(sheet, args, quarter, np.zeros(3)).faces, single)
 
 
 def test_the_scripts_know_the_flags_and_refuse_bad_values(tmp_path, capsys):
@@ -404,7 +404,9 @@ def test_the_scripts_know_the_flags_and_refuse_bad_values(tmp_path, capsys):
     assert not os.path.exists(out)
     # the stage runs between the component filter and the smoothing
     import inspect
+    from raynet_amd.scripts import mesh_flags
+    stages = inspect.getsource(mesh_flags.apply)
+    assert stages.index("drop_components(") < stages.index("simplify(") < stages.index("smooth(")
     for script in (fuse_depth_maps, render_volume):
         body = inspect.getsource(script.main)
-        assert body.index("component_flags.apply(") < body.index("simplify_flags.apply(") < \
-            body.index("smooth_flags.apply(") < body.index("compute_normals()")
+        assert body.index("mesh_flags.apply(") < body.index("compute_normals()")

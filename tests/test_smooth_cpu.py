@@ -255,23 +255,23 @@ def test_boundary_vertices_by_the_torch_route_is_the_truths():
 
 # ------------------------------------------------------------------------------ the scripts
 def test_the_flag_helper_smooths_and_reports(truth_steps, capsys, tmp_path):
-    from raynet_amd.scripts import fuse_depth_maps, smooth_flags
+    from raynet_amd.scripts import fuse_depth_maps, mesh_flags
     from raynet_amd.volume import SurfaceMesh
     vertices, faces = _open_mesh(4)
     mesh = SurfaceMesh(vertices, faces)
     voxel = np.array([0.5, 0.25, 1.0])
     # without --smooth: the very object, nothing printed, and so the bytes of the file
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply"])
-    assert smooth_flags.given(args) == []
-    assert smooth_flags.apply(mesh, args, voxel) is mesh and capsys.readouterr().out == ""
+    assert mesh_flags.given(args) == []
+    assert mesh_flags.smooth(mesh, args, voxel) is mesh and capsys.readouterr().out == ""
     assert truth_steps == []
     before, after = str(tmp_path / "before.ply"), str(tmp_path / "after.ply")
     mesh.save_ply(before)
-    smooth_flags.apply(mesh, args, voxel).save_ply(after)
+    mesh_flags.smooth(mesh, args, voxel).save_ply(after)
     assert open(before, "rb").read() == open(after, "rb").read()
     # --smooth 3: the defaults -- lambda 0.5, mu -0.53, one side of the smallest voxel, border pinned
     args = fuse_depth_maps.build_parser().parse_args(["s", "p", "o.ply", "--smooth", "3"])
-    out = smooth_flags.apply(mesh, args, voxel)
+    out = mesh_flags.smooth(mesh, args, voxel)
     border = st.boundary_vertices(faces, len(vertices))
     want = st.smooth(vertices, faces, 3, 0.5, -0.53, border, 0.25)
     assert np.array_equal(_bits(out.vertices), _bits(want))
@@ -282,12 +282,12 @@ def test_the_flag_helper_smooths_and_reports(truth_steps, capsys, tmp_path):
     args = fuse_depth_maps.build_parser().parse_args([
         "s", "p", "o.ply", "--smooth", "2", "--smooth_lambda", "0.6", "--smooth_mu", "0",
         "--smooth_max_move", "inf", "--smooth_free_boundary"])
-    out = smooth_flags.apply(mesh, args, voxel)
+    out = mesh_flags.smooth(mesh, args, voxel)
     assert np.array_equal(_bits(out.vertices), _bits(st.smooth(vertices, faces, 2, 0.6, 0.0)))
     assert truth_steps[-1]["fixed"] is None and truth_steps[-1]["max_move"] == np.inf
     args = fuse_depth_maps.build_parser().parse_args([
         "s", "p", "o.ply", "--smooth", "2", "--smooth_max_move", "0.1"])
-    out = smooth_flags.apply(mesh, args, voxel)
+    out = mesh_flags.smooth(mesh, args, voxel)
     assert truth_steps[-1]["max_move"] == 0.1 * 0.25
     assert np.abs(out.vertices.astype(np.float64) - vertices).max() <= 0.025 + 1e-6
 
