@@ -1167,6 +1167,74 @@ int rn_mesh_simplify(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t 
                      float *vertices_out, int32_t *faces_out, int32_t *source, int32_t *cluster,
                      int64_t *counts, void *workspace, void *stream);
 
+/* ---- the small holes of an indexed triangle mesh capped ----
+ *
+ * rn_mesh_fill_holes: every simple boundary loop of at most max_edges edges gets a vertex at the
+ * mean of its vertices and a fan of faces from that vertex to its edges.
+ *
+ * All arrays are device memory.  vertices [nv][3] f32, faces [nf][3] i32 and the corner table
+ * (offsets [nv + 1] i32, corners [3 nf] i32: the indices c = 3 face + slot of the flattened faces
+ * sorted by the vertex they name, and the exclusive prefix of the vertices' corner counts) are
+ * never written.  The caller allocates the upper bounds:
+ *   new_vertices [nf][3]   f32   the centre of every filled loop
+ *   new_faces    [3 nf][3] i32   the faces of the caps, of indices into cat(vertices, new_vertices)
+ *   source       [nf]      i32   the label of every filled loop
+ *   counts       [5]       i64   filled loops, new faces, loops, loops not simple, boundary
+ *                                half-edges
+ * Only the first counts[0] rows of new_vertices and source and the first counts[1] rows of
+ * new_faces are written; the rest keep their bits.  The caller's mesh after the call is
+ * cat(vertices, new_vertices[:counts[0]]) and cat(faces, new_faces[:counts[1]]): the input's order
+ * is kept, so per-vertex attributes carry over by position.  workspace: 8-byte aligned, at least
+ * rn_mesh_fill_holes_workspace_bytes(nv, nf) bytes (-1 for sizes rn_mesh_fill_holes refuses), laid
+ * out scan [nv] u64 | the scan's scratch | total [1] u64 | partial [256][3] i64 | parent, out_deg,
+ * in_deg, out_edge, edges, bad [nv] i32 each | status [2] i32 | boundary [3 nf] u8.  Nothing beyond that size is touched.
+ *
+ * A face COUNTS iff its three indices lie in [0, nv) and differ pairwise.
+ *
+ * The half-edge h = 3 f + s of a counting face goes from a = faces[f][s] to b = faces[f][(s + 1) %
+ * 3].  Over the corners of the counting faces around a, count how often b occurs among the two
+ * other vertices of those faces: h is a BOUNDARY half-edge iff that count is exactly 1, that is,
+ * iff the undirected edge {a, b} lies in one counting face.  (Duplicate faces have no boundary
+ * edges.  The count is the same from either end; the kernel scans the corner list of the end with
+ * fewer corners.)
+ *
+ * The boundary half-edges form a directed graph on the vertices.  A LOOP is a connected component
+ * of that graph -- two vertices are connected if a boundary half-edge joins them, in either
+ * direction; its LABEL is its smallest vertex, E the number of its boundary half-edges.  A loop is
+ * SIMPLE iff every vertex that is an end of one of its half-edges has exactly one outgoing
+ * boundary half-edge, exactly one incoming one, and three finite coordinates; such a loop is one
+ * directed cycle.  Two holes that meet at a vertex, a rim with a flipped face and a loop through a
+ * NaN vertex are not simple and stay open, as a whole.  A loop is FILLED iff it is simple and
+ * 3 <= E <= max_edges.  The filled loops are numbered k = 0, 1, ... in ascending label.
+ *
+ * Filling loop k with label r: walk v_0 = r, v_{j+1} = the head of v_j's outgoing boundary
+ * half-edge, for j < E.  The centre is, per axis, the fp64 sum of (double) v_j's f32 coordinate in
+ * the walk's order, from 0.0, divided once by (double) E in fp64 and rounded once to f32 (the
+ * library is built with -ffp-contract=off; tests/holes_truth.py restates it in NumPy to the bit).
+ * new_vertices[k] = the centre, source[k] = r, and the faces (v_{j+1}, v_j, nv + k) for j = 0 ..
+ * E - 1, in that order, from row (the sum of E over the filled loops before k) of new_faces: each
+ * runs against its boundary half-edge, so the winding is the mesh's.
+ *
+ * The result is one fixed set of arrays whatever the launch geometry or the order in which the
+ * hardware ran the threads (integer atomics only).  Whatever faces, offsets, corners and the
+ * positions hold, nothing is read or written out of bounds, no loop waits for another thread, and
+ * every chase is bounded (raynet_amd/csrc/raynet_holes_args.h has the proof).  The entry waits for
+ * the stream once: RN_ERR_STATE if a chase or a walk met what the definition rules out, which no
+ * input can cause.
+ *
+ * nv == 0 or nf == 0: RN_OK, counts cleared, no kernel launch.  RN_ERR_INVALID, rn_last_error
+ * naming the entry, no launch, outputs untouched: nv or nf negative, nv > 2^31 - 2, 3 nf > 2^31 -
+ * 1, nv + nf > 2^31 - 2 (a new vertex nv + k is an int32), max_edges < 3 or > 65536, a NULL counts,
+ * and with nv > 0 and nf > 0 any other NULL array, a workspace that is not 8-byte aligned, an
+ * output (new_vertices, new_faces, source, counts, workspace) that shares a byte with an input or
+ * with another output. */
+int64_t rn_mesh_fill_holes_workspace_bytes(int64_t nv, int64_t nf);
+int rn_mesh_fill_holes(rn_ctx *ctx, int64_t nv, const float *vertices, int64_t nf,
+                       const int32_t *faces, const int32_t *offsets, const int32_t *corners,
+                       int32_t max_edges,
+                       float *new_vertices, int32_t *new_faces, int32_t *source, int64_t *counts,
+                       void *workspace, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

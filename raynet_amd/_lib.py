@@ -53,6 +53,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
             os.path.join(CSRC, "raynet_simplify.inl"),
             os.path.join(CSRC, "raynet_simplify_args.h"),
+            os.path.join(CSRC, "raynet_holes.inl"), os.path.join(CSRC, "raynet_holes_args.h"),
             os.path.join(CSRC, "raynet_mesh_args.h"),
             os.path.join(CSRC, "raynet_scan.inl"), os.path.join(CSRC, "raynet_scan_args.h"),
             HEADER]
@@ -228,6 +229,8 @@ SIGNATURES = {
     "rn_mesh_smooth": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],
     "rn_mesh_simplify_workspace_bytes": [_L, _L, _P],
     "rn_mesh_simplify": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_fill_holes_workspace_bytes": [_L, _L],
+    "rn_mesh_fill_holes": [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],
@@ -266,5 +269,6 @@ def load():
     lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_simplify_workspace_bytes.restype = ctypes.c_int64
+    lib.rn_mesh_fill_holes_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib

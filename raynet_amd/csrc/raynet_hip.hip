@@ -1254,5 +1254,9 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // section 24)
 #include "raynet_simplify.inl"
 
+// the small holes of a surface mesh capped: the union-find over the boundary half-edges, the
+// corner table and the scan
+#include "raynet_holes.inl"
+
 // the surface of a belief grid: marching tetrahedra and the scan
 #include "raynet_isosurface.inl"

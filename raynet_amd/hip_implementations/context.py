@@ -527,6 +527,46 @@ class HipContext(object):
         nv_out, nf_out = (int(x) for x in counts.tolist())
         return vertices_out[:nv_out], faces_out[:nf_out], source[:nv_out], cluster
 
+    # ---- small holes of a mesh capped (raynet_amd/holes.py) ------------------------------------
+    def mesh_fill_holes_workspace_bytes(self, nv, nf):
+        """rn_mesh_fill_holes_workspace_bytes: the bytes rn_mesh_fill_holes needs for nv vertices
+        and nf faces."""
+        n = int(self.lib.rn_mesh_fill_holes_workspace_bytes(int(nv), int(nf)))
+        if n < 0:
+            raise ValueError("rn_mesh_fill_holes_workspace_bytes: bad sizes (nv %d, nf %d)" % (nv, nf))
+        return n
+
+    def mesh_fill_holes(self, vertices, faces, offsets, corners, max_edges, workspace=None):
+        """rn_mesh_fill_holes: vertices (nv, 3) f32, faces (nf, 3) i32, the corner table (offsets
+        [nv + 1] i32, corners [3 nf] i32), max_edges in 3..65536 -> (new_vertices (k, 3) f32,
+        new_faces (m, 3) i32, source [k] i32, counts [5] int64 on the host): every simple boundary
+        loop of at most max_edges edges gets a vertex at the mean of its vertices (new_vertices,
+        index nv + its row) and a fan of faces; source: the loops' smallest vertices; counts:
+        filled loops, new faces, loops, loops not simple, boundary half-edges.  workspace: a uint8
+        tensor of at least mesh_fill_holes_workspace_bytes(nv, nf) bytes, 8-byte aligned
+        (allocated if None).  One read-back: the counts come back to slice the outputs."""
+        nv, nf = len(vertices), len(faces)
+        _chk(vertices, torch.float32, 3 * nv, "vertices")
+        _chk(faces, torch.int32, 3 * nf, "faces")
+        _chk(offsets, torch.int32, nv + 1, "offsets")
+        _chk(corners, torch.int32, 3 * nf, "corners")
+        need = self.mesh_fill_holes_workspace_bytes(nv, nf)
+        if workspace is None:
+            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
+        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        device = vertices.device
+        new_vertices = torch.empty((nf, 3), dtype=torch.float32, device=device)
+        new_faces = torch.empty((3 * nf, 3), dtype=torch.int32, device=device)
+        source = torch.empty((nf,), dtype=torch.int32, device=device)
+        counts = torch.empty((5,), dtype=torch.int64, device=device)
+        self._check(self.lib.rn_mesh_fill_holes(
+            self._h, nv, _ptr(vertices), nf, _ptr(faces), _ptr(offsets), _ptr(corners),
+            int(max_edges), _ptr(new_vertices), _ptr(new_faces), _ptr(source), _ptr(counts),
+            _ptr(workspace), _stream()))
+        counts = counts.cpu().numpy()
+        k, m = int(counts[0]), int(counts[1])
+        return new_vertices[:k], new_faces[:m], source[:k], counts
+
     # -- timing (bench.py): hipEvents on the stream the kernels run on ------
     def timer_start(self):
         self._check(self.lib.rn_timer_start(self._h, _stream()))

@@ -30,7 +30,8 @@ observation ends.
                      compute_metrics scores
 the mesh-cleanup flags
                      drop the floaters (--min_component_faces, --min_component_fraction,
-                     --keep_largest), then --simplify the surface, then --smooth it, before
+                     --keep_largest), then cap the small holes (--fill_holes N), then
+                     --simplify the surface, then --smooth it, before
                      normals, colours and --mesh_cloud: see raynet_amd.scripts.mesh_flags
 """
 import argparse

@@ -1,5 +1,5 @@
 """The flags that clean up a mesh before it is written, shared by fuse_depth_maps and render_volume
---mesh.  Three stages, in this order, each on the cleaned mesh and before normals, colours and
+--mesh.  Four stages, in this order, each on the cleaned mesh and before normals, colours and
 --mesh_cloud:
 
 --min_component_faces N      drop the connected components with fewer than N faces
@@ -7,6 +7,15 @@
 --keep_largest K             keep only the K components with the most faces
     Two vertices are connected if a face names both (raynet_amd.components).
     Prints `components: K found, k kept, F -> f faces`.
+
+--fill_holes N               cap every simple boundary loop of 3..N edges (N in 3..65536) with a
+                             vertex at the mean of its vertices and a fan of faces; longer loops
+                             -- the outer rim of the surface -- and loops that are not simple stay
+                             open.  After the component filter, so that the rim of a stray patch is
+                             not capped into a pillow; before --simplify and --smooth, which then
+                             treat the caps like the rest and find no rim to pin
+    (raynet_amd.holes).  Prints
+    `holes: K loops, k filled (s not simple, l longer than N), F -> F' faces`.
 
 --simplify X                 vertex clustering: the vertices that share a cell of X voxel sides of
                              the grid per axis (a positive, finite number) become one vertex at
@@ -34,7 +43,9 @@ COMPONENT_FLAGS = ("min_component_faces", "min_component_fraction", "keep_larges
 SIMPLIFY_FLAGS = ("simplify", "simplify_keep_duplicates")
 SMOOTH_FLAGS = ("smooth", "smooth_lambda", "smooth_mu", "smooth_max_move", "smooth_free_boundary")
 FLAGS = COMPONENT_FLAGS + SIMPLIFY_FLAGS + SMOOTH_FLAGS
+HOLE_FLAGS = ("fill_holes",)        # registered behind FLAGS; its stage runs after the components'
 MAX_ITERATIONS = 10000
+MIN_HOLE_EDGES, MAX_HOLE_EDGES = 3, 65536
 
 
 def add_arguments(p):
@@ -59,6 +70,8 @@ def add_arguments(p):
                         "smallest voxel (1; inf: no limit)")
     p.add_argument("--smooth_free_boundary", action="store_true", default=None,
                    help="--smooth: do not pin the vertices on the border of the mesh")
+    p.add_argument("--fill_holes", type=int, default=None,
+                   help="Cap the boundary loops of the mesh that have at most this many edges")
 
 
 def given(args, flags=FLAGS):
@@ -81,6 +94,12 @@ def check(parser, args, mesh_requested=True):
     if x is not None and not (math.isfinite(x) and 0.0 < x <= 1.0):
         parser.error("--min_component_fraction takes a fraction in (0, 1]")
     needs_mesh(COMPONENT_FLAGS, "components are")
+
+    n = getattr(args, "fill_holes", None)
+    if n is not None and not MIN_HOLE_EDGES <= n <= MAX_HOLE_EDGES:
+        parser.error("--fill_holes takes a number of edges, %d..%d" % (MIN_HOLE_EDGES, MAX_HOLE_EDGES))
+    if not mesh_requested and n is not None:
+        parser.error("--fill_holes goes with --mesh PATH: the holes are the mesh's")
 
     x = args.simplify
     if x is not None and not (math.isfinite(x) and x > 0.0):
@@ -121,6 +140,20 @@ def drop_components(mesh, args):
                                     args.keep_largest)
     print("components: %d found, %d kept, %d -> %d faces"
           % (found, kept, len(mesh.faces), len(out.faces)))
+    return out
+
+
+def fill_holes(mesh, args):
+    """The mesh with its small holes capped; the mesh itself without --fill_holes (and for a
+    namespace that does not know the flag).  Prints the tally."""
+    n = getattr(args, "fill_holes", None)
+    if n is None:
+        return mesh
+    out, stats = mesh.filled(n, return_stats=True)
+    print("holes: %d loops, %d filled (%d not simple, %d longer than %d), %d -> %d faces"
+          % (stats["loops"], stats["filled"], stats["not_simple"],
+             stats["loops"] - stats["filled"] - stats["not_simple"], n, len(mesh.faces),
+             len(out.faces)))
     return out
 
 
@@ -167,8 +200,10 @@ def smooth(mesh, args, voxel):
 
 def apply(mesh, args, volume):
     """The mesh of `volume` (its bbox and grid_shape give the voxel) through the stages whose flags
-    are given: components, then simplify, then smooth.  The mesh itself if no flag is."""
+    are given: components, then fill_holes, then simplify, then smooth.  The mesh itself if no
+    flag is."""
     voxel = voxel_sides(volume)
     mesh = drop_components(mesh, args)
+    mesh = fill_holes(mesh, args)
     mesh = simplify(mesh, args, voxel, volume.bbox.astype(np.float64)[:3])
     return smooth(mesh, args, voxel)

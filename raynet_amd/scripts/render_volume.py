@@ -32,7 +32,8 @@ vertex lies on an edge of a lattice cell, and the surface point its nearest pixe
 the same or the next cell unless the view is grazing).
 
 The mesh-cleanup flags, with --mesh: drop the floaters (--min_component_faces,
---min_component_fraction, --keep_largest), then --simplify the surface, then --smooth it, before
+--min_component_fraction, --keep_largest), then cap the small holes (--fill_holes N), then
+--simplify the surface, then --smooth it, before
 colours and --mesh_cloud: see raynet_amd.scripts.mesh_flags.
 """
 import argparse

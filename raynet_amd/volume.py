@@ -130,6 +130,26 @@ class SurfaceMesh(object):
         from . import components
         return components.filter_small(self, min_faces, min_fraction, keep_largest)[0]
 
+    # ---- small holes capped (holes.py) --------------------------------
+    def filled(self, max_edges, return_stats=False):
+        """-> a new SurfaceMesh with every simple boundary loop of 3..max_edges edges capped by a
+        vertex at the mean of its vertices and a fan of faces (holes.fill_holes); with
+        return_stats, (the mesh, the dict of the five counts).  This mesh's vertices and faces
+        come first, in their order; a centre takes the colour of its loop's smallest vertex,
+        normals are recomputed if and only if this mesh has them.  An empty mesh gives an empty
+        mesh, without the GPU."""
+        from . import holes
+        if self.empty:
+            holes.check_max_edges(max_edges)
+            out = SurfaceMesh(self.vertices.copy(), self.faces.copy(), self.normals, self.colors)
+            return (out, dict.fromkeys(holes.COUNTS, 0)) if return_stats else out
+        vertices, faces, source, stats = holes.fill_holes(self.vertices, self.faces, max_edges)
+        colors = None if self.colors is None else np.concatenate([self.colors, self.colors[source]])
+        out = SurfaceMesh(vertices, faces, None, colors)
+        if self.normals is not None:
+            out.compute_normals()
+        return (out, stats) if return_stats else out
+
     # ---- simplification (simplify.py, DESIGN.md section 24) ---------------------------------
     def simplified(self, cell, origin=None, drop_duplicate_faces=True):
         """-> a new SurfaceMesh with the vertices of every cell of a uniform grid (sides `cell`, a
