@@ -54,6 +54,27 @@ def _chk(t, dtype, min_numel=0, name="tensor", optional=False, align=4):
     return t
 
 
+def _chk_mesh(vertices, faces, *table):
+    """A mesh as the mesh entries take it: vertices (nv, 3) f32, faces (nf, 3) i32 and, where the
+    entry reads one, the corner table (offsets [nv + 1] i32, corners [3 nf] i32) -> (nv, nf)."""
+    nv, nf = len(vertices), len(faces)
+    _chk(vertices, torch.float32, 3 * nv, "vertices")
+    _chk(faces, torch.int32, 3 * nf, "faces")
+    if table:
+        offsets, corners = table
+        _chk(offsets, torch.int32, nv + 1, "offsets")
+        _chk(corners, torch.int32, 3 * nf, "corners")
+    return nv, nf
+
+
+def _workspace(workspace, need, device):
+    """The uint8 workspace of an entry that reports `need` bytes: the given one, at least that
+    long and 8-byte aligned, or a fresh one (never empty: the entry wants a pointer)."""
+    if workspace is None:
+        return torch.empty((max(need, 8),), dtype=torch.uint8, device=device)
+    return _chk(workspace, torch.uint8, need, "workspace", align=8)
+
+
 def _three_ints(x, name):
     """Three whole numbers of a host array argument (dims), each an int32."""
     a = np.asarray(x)
@@ -358,11 +379,7 @@ class HipContext(object):
         """rn_vertex_area_normals: vertices (nv, 3) f32, faces (nf, 3) i32 and the mesh's corner
         table by vertex (offsets [nv + 1] i32, corners [3 nf] i32) -> normals (nv, 3) f32, the
         area-weighted sums of the face normals around every vertex (not normalised)."""
-        nv, nf = len(vertices), len(faces)
-        _chk(vertices, torch.float32, 3 * nv, "vertices")
-        _chk(faces, torch.int32, 3 * nf, "faces")
-        _chk(offsets, torch.int32, nv + 1, "offsets")
-        _chk(corners, torch.int32, 3 * nf, "corners")
+        nv, nf = _chk_mesh(vertices, faces, offsets, corners)
         if normals is None:
             normals = torch.empty((nv, 3), dtype=torch.float32, device=vertices.device)
         _chk(normals, torch.float32, 3 * nv, "normals")
@@ -467,16 +484,10 @@ class HipContext(object):
         Taubin iterations (a step with `lam`, then one with `mu` unless it is 0), no coordinate
         farther than `max_move` from where it started.  workspace: a uint8 tensor of at least
         mesh_smooth_workspace_bytes(nv, nf) bytes, 8-byte aligned (allocated if None)."""
-        nv, nf = len(vertices), len(faces)
-        _chk(vertices, torch.float32, 3 * nv, "vertices")
-        _chk(faces, torch.int32, 3 * nf, "faces")
-        _chk(offsets, torch.int32, nv + 1, "offsets")
-        _chk(corners, torch.int32, 3 * nf, "corners")
+        nv, nf = _chk_mesh(vertices, faces, offsets, corners)
         _chk(fixed, torch.uint8, nv, "fixed", optional=True, align=1)
         need = self.mesh_smooth_workspace_bytes(nv, nf)
-        if workspace is None:
-            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
-        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        workspace = _workspace(workspace, need, vertices.device)
         if out is None:
             out = torch.empty((nv, 3), dtype=torch.float32, device=vertices.device)
         _chk(out, torch.float32, 3 * nv, "out")
@@ -505,16 +516,12 @@ class HipContext(object):
         workspace: a uint8 tensor of at least mesh_simplify_workspace_bytes(nv, nf, dims) bytes,
         8-byte aligned (allocated if None).  Synchronises the stream once: the two counts come
         back to slice the outputs."""
-        nv, nf = len(vertices), len(faces)
-        _chk(vertices, torch.float32, 3 * nv, "vertices")
-        _chk(faces, torch.int32, 3 * nf, "faces")
+        nv, nf = _chk_mesh(vertices, faces)
         d = (ctypes.c_int32 * 3)(*_three_ints(dims, "dims"))
         o = (ctypes.c_double * 3)(*_three_floats(origin, "origin"))
         c = (ctypes.c_double * 3)(*_three_floats(cell, "cell"))
         need = self.mesh_simplify_workspace_bytes(nv, nf, dims)
-        if workspace is None:
-            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
-        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        workspace = _workspace(workspace, need, vertices.device)
         device = vertices.device
         vertices_out = torch.empty((nv, 3), dtype=torch.float32, device=device)
         faces_out = torch.empty((nf, 3), dtype=torch.int32, device=device)
@@ -545,15 +552,9 @@ class HipContext(object):
         filled loops, new faces, loops, loops not simple, boundary half-edges.  workspace: a uint8
         tensor of at least mesh_fill_holes_workspace_bytes(nv, nf) bytes, 8-byte aligned
         (allocated if None).  One read-back: the counts come back to slice the outputs."""
-        nv, nf = len(vertices), len(faces)
-        _chk(vertices, torch.float32, 3 * nv, "vertices")
-        _chk(faces, torch.int32, 3 * nf, "faces")
-        _chk(offsets, torch.int32, nv + 1, "offsets")
-        _chk(corners, torch.int32, 3 * nf, "corners")
+        nv, nf = _chk_mesh(vertices, faces, offsets, corners)
         need = self.mesh_fill_holes_workspace_bytes(nv, nf)
-        if workspace is None:
-            workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=vertices.device)
-        _chk(workspace, torch.uint8, need, "workspace", align=8)
+        workspace = _workspace(workspace, need, vertices.device)
         device = vertices.device
         new_vertices = torch.empty((nf, 3), dtype=torch.float32, device=device)
         new_faces = torch.empty((3 * nf, 3), dtype=torch.int32, device=device)

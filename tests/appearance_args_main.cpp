@@ -11,17 +11,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_appearance_args.h"
+#include "host_main.h"
 
 using namespace rn_app;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 // what an entry returns for a verdict, before it launches anything
 static int status(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
@@ -174,7 +166,5 @@ int main() {
     // 32 views of 16384 x 16384 x 4: beyond 32 bits, within size_t
     EXPECT(image_index(31, 16383, 16383, 3, 16384, 16384, 4) == 32ULL * 16384 * 16384 * 4 - 1);
     EXPECT(MAX_VIEWS == 32 && MAX_CHANNELS == 4 && CAMERA_DOUBLES == 15);
-    if (failures) return 1;
-    std::printf("appearance_args: ok\n");
-    return 0;
+    return finish("appearance");
 }

@@ -16,17 +16,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_components_args.h"
+#include "host_main.h"
 
 using namespace rn_cc;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 // what the entry returns for a verdict, before it launches anything
 static int status(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
@@ -259,7 +251,5 @@ int main() {
         copy = parent;
         EXPECT(!unite(at, 7, 0, 0));
     }
-    if (failures) return 1;
-    std::printf("components_args: ok\n");
-    return 0;
+    return finish("components");
 }

@@ -11,17 +11,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_fusion_args.h"
+#include "host_main.h"
 
 using namespace rn_fusion;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 // what the entry returns for a verdict, before it launches anything
 static int status(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
@@ -142,7 +134,5 @@ int main() {
     EXPECT(map_extent(4096, 4096, 4096) == (1ULL << 36));
     EXPECT(map_index(4095, 46340, 46340, 46341, 46341) == 4096ULL * 46341 * 46341 - 1);
     EXPECT(MAX_VIEWS == 4096 && CAMERA_DOUBLES == 15);
-    if (failures) return 1;
-    std::printf("fusion_args: ok\n");
-    return 0;
+    return finish("fusion");
 }

@@ -21,17 +21,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_holes_args.h"
+#include "host_main.h"
 
 using namespace rn_hl;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 static int status_of(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
 
@@ -495,7 +487,5 @@ int main() {
                 EXPECT(by_phases(holes, off, cor, 10, backwards).ok);
         }
     }
-    if (failures) return 1;
-    std::printf("holes_args: ok\n");
-    return 0;
+    return finish("holes");
 }

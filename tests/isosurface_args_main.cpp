@@ -12,17 +12,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_isosurface_args.h"
+#include "host_main.h"
 
 using namespace rn_iso;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 // what an entry returns for a verdict, before it launches anything
 static int status(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
@@ -141,7 +133,5 @@ int main() {
     const uint64_t sum = (uint64_t)178453547 * w;
     EXPECT(count_vertices(sum) == 7LL * 178453547 && count_faces(sum) == 12LL * 178453547);
     EXPECT(count_faces(sum) < (1LL << 31));
-    if (failures) return 1;
-    std::printf("isosurface_args: ok\n");
-    return 0;
+    return finish("isosurface");
 }

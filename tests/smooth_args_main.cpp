@@ -22,17 +22,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_smooth_args.h"
+#include "host_main.h"
 
 using namespace rn_sm;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 static const double INF = std::numeric_limits<double>::infinity();
 static const double NaN = std::numeric_limits<double>::quiet_NaN();
@@ -259,13 +251,6 @@ static Mesh planted(Mesh m, unsigned seed) {
 }
 
 // ------------------------------------------------------------------------------ two smoothings
-template <class T>
-static std::unique_ptr<T[]> exact(const std::vector<T> &from) {
-    std::unique_ptr<T[]> p(new T[from.size()]);         // exactly sized: one past is an error
-    std::copy(from.begin(), from.end(), p.get());
-    return p;
-}
-
 // as rn_mesh_smooth runs it: the header's functions, "launch" by "launch", in exactly-sized buffers
 static std::vector<float> by_the_header(const Mesh &m, int32_t iterations, double lambda, double mu,
                                         double max_move) {
@@ -423,10 +408,5 @@ int main() {
     check_verdicts();
     check_layout_and_parity();
     check_smoothings();
-    if (failures) {
-        std::printf("smooth_args: %d expectation(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("smooth_args: ok\n");
-    return 0;
+    return finish("smooth");
 }

@@ -6,7 +6,6 @@ undefined-behaviour sanitizers -- nothing sanitised is loaded into this interpre
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import pytest
 import appearance_truth as at
 import isosurface_truth as it
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 
@@ -75,14 +75,7 @@ def test_the_kernel_file_is_plain_hip_and_listed():
 
 
 def test_launcher_checks_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "appearance_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(REPO, "raynet_amd", "csrc"),
-                           os.path.join(REPO, "tests", "appearance_args_main.cpp"), "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("appearance_args: ok"), r.stdout
+    run_host_program("appearance", tmp_path)
 
 
 # ------------------------------------------------------------------------- SurfaceMesh's file

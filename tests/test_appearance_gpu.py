@@ -11,23 +11,13 @@ import pytest
 
 import appearance_truth as at
 import isosurface_truth as it
+import mesh_harness as h
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 D = np.float64
-PAD = 5
 NS = (0, 1, 63, 64, 65, 257, 300)
-
-
-def _ctx():
-    from raynet_amd.hip_implementations import get_context
-    return get_context()
-
-
-def _cuda(a, dtype=None):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _project(ctx, n, points, normals, cameras, images, depths, tol, min_cos, border, mode,
@@ -40,16 +30,15 @@ def _project(ctx, n, points, normals, cameras, images, depths, tol, min_cos, bor
     V = 0 if cameras is None else len(cameras)
     if images is not None:
         H, W, C = (int(s) for s in images.shape[1:])
-    colors = torch.full((n + PAD, C), -7.0, dtype=torch.float32, device="cuda")
-    weight = torch.full((n + PAD,), -7.0, dtype=torch.float32, device="cuda")
-    views = torch.full((n + PAD,), -7, dtype=torch.int32, device="cuda")
+    colors = h.padded((n, C), -7.0, torch.float32)
+    weight, views = h.padded(n, -7.0, torch.float32), h.padded(n, -7, torch.int32)
     ctx._check(ctx.lib.rn_project_colors(
         ctx._h, n, _ptr(points), _ptr(normals), V, _ptr(cameras), H, W, C, _ptr(images),
         _ptr(depths), float(tol), float(min_cos), float(border), int(mode), _ptr(colors),
         _ptr(weight), _ptr(views), _stream()))
     c, w, m = colors.cpu().numpy(), weight.cpu().numpy(), views.cpu().numpy()
-    assert (c[n:] == -7).all() and (w[n:] == -7).all() and (m[n:] == -7).all(), \
-        "written beyond the rows asked for"
+    for out in (c, w, m):
+        h.assert_untouched(out, n, -7, "written beyond the rows asked for")
     return c[:n], w[:n], m[:n].view(np.uint32)
 
 
@@ -96,10 +85,10 @@ def test_colours_are_the_restatement_bit_for_bit(V, HW, C):
     point's row does not depend on n, so the truth is computed once per setting for the 300
     points and every smaller n is its prefix."""
     H, W = HW
-    ctx = _ctx()
+    ctx = h.ctx()
     points, normals, cameras, images, depths = _scene(V, H, W, C, seed=100 * V + 10 * H + C)
-    d_points, d_normals = _cuda(points), _cuda(normals)
-    d_cameras, d_images, d_depths = _cuda(cameras), _cuda(images), _cuda(depths)
+    d_points, d_normals = h.cuda(points), h.cuda(normals)
+    d_cameras, d_images, d_depths = h.cuda(cameras), h.cuda(images), h.cuda(depths)
     if V == 0:
         d_cameras = d_images = d_depths = None
     counted = 0
@@ -124,9 +113,9 @@ def test_colours_are_the_restatement_bit_for_bit(V, HW, C):
 
 
 def test_blend_and_best_share_weights_and_masks():
-    ctx = _ctx()
+    ctx = h.ctx()
     points, normals, cameras, images, depths = _scene(5, 24, 32, 3, seed=7)
-    dev = [_cuda(a) for a in (points, normals, cameras, images, depths)]
+    dev = [h.cuda(a) for a in (points, normals, cameras, images, depths)]
     blend = _project(ctx, 300, *dev, 0.05, 0.0, 0.0, 0)
     best = _project(ctx, 300, *dev, 0.05, 0.0, 0.0, 1)
     assert np.array_equal(blend[1].view(np.int32), best[1].view(np.int32))
@@ -146,9 +135,9 @@ def test_planted_points_depths_normals_and_ties():
     depth lookup, NaN and infinite coordinates, depths 0 / negative / NaN / +inf, normals zero,
     facing away and exactly perpendicular, and two views of exactly equal weight.  The conditions
     are check_planted's, which tests/test_appearance_truth.py holds the truth to."""
-    ctx = _ctx()
+    ctx = h.ctx()
     scene = at.planted_scene()
-    dev = [_cuda(scene[k]) for k in ("points", "normals", "cameras", "images", "depths")]
+    dev = [h.cuda(scene[k]) for k in ("points", "normals", "cameras", "images", "depths")]
     for mode in (0, 1):
         want = at.project_colors(scene["points"], scene["normals"], scene["cameras"],
                                  scene["images"], scene["depths"], 0.0, 0.0, 0.0, mode)
@@ -158,19 +147,19 @@ def test_planted_points_depths_normals_and_ties():
 
 
 def test_one_sided_occlusion_with_a_tolerance():
-    ctx = _ctx()
+    ctx = h.ctx()
     cams, images, depths = at.plane_scene()
     cameras = at.pack_cameras(cams)
     rng = np.random.default_rng(11)
     pts = np.zeros((257, 3), F)
     pts[:, 0] = rng.uniform(-3.0, 3.0, 257)
     pts[:, 1] = rng.uniform(-2.4, 2.4, 257)
-    dev = [_cuda(a) for a in (cameras, images, depths)]
+    dev = [h.cuda(a) for a in (cameras, images, depths)]
     for z, tol in ((0.0, 0.1), (0.5, 0.0), (-0.5, 0.1), (-0.05, 0.1)):
         p = pts.copy()
         p[:, 2] = z
         want = at.project_colors(p, None, cameras, images, depths, tol, 0.0, 0.0, 0)
-        got = _project(ctx, 257, _cuda(p), None, *dev, tol, 0.0, 0.0, 0)
+        got = _project(ctx, 257, h.cuda(p), None, *dev, tol, 0.0, 0.0, 0)
         _same(got, want, ("plane", z, tol))
         if z == -0.5:
             assert (got[2] == 0).all()
@@ -178,7 +167,7 @@ def test_one_sided_occlusion_with_a_tolerance():
             assert (got[2] != 0).sum() > 100
     # the plane's colours come back within the float32 rounding of its images
     want = at.affine_field(pts[:, 0].astype(D), pts[:, 1].astype(D))
-    got = _project(ctx, 257, _cuda(pts), None, *dev, 0.1, 0.0, 0.0, 0)
+    got = _project(ctx, 257, h.cuda(pts), None, *dev, 0.1, 0.0, 0.0, 0)
     seen = got[2] != 0
     assert np.abs(got[0][seen].astype(D) - want[seen]).max() <= 1e-6
 
@@ -189,15 +178,15 @@ def _normals(ctx, vertices, faces, offsets, corners, nv=None, nf=None):
     from raynet_amd.hip_implementations.context import _ptr, _stream
     nv = len(vertices) if nv is None else nv
     nf = len(faces) if nf is None else nf
-    out = torch.full((nv + PAD, 3), -7.0, dtype=torch.float32, device="cuda")
+    out = h.padded((nv, 3), -7.0, torch.float32)
     # (held in names until the copy back: a tensor nobody holds returns its memory at once)
-    dv, df = _cuda(vertices, F), _cuda(faces, np.int32)
-    do, dc = _cuda(offsets, np.int32), _cuda(corners, np.int32)
+    dv, df = h.cuda(vertices, F), h.cuda(faces, np.int32)
+    do, dc = h.cuda(offsets, np.int32), h.cuda(corners, np.int32)
     ctx._check(ctx.lib.rn_vertex_area_normals(ctx._h, nv, _ptr(dv), nf, _ptr(df), _ptr(do),
                                               _ptr(dc), _ptr(out), _stream()))
     got = out.cpu().numpy()
     del dv, df, do, dc
-    assert (got[nv:] == -7).all(), "written beyond the vertices"
+    h.assert_untouched(got, nv, -7, "written beyond the vertices")
     return got[:nv]
 
 
@@ -230,7 +219,7 @@ def test_area_normals_are_the_restatement_bit_for_bit(meshes, name):
     d_off, d_cor = corner_table(torch.from_numpy(f).cuda(), len(v))
     assert np.array_equal(d_off.cpu().numpy(), offsets) and np.array_equal(d_cor.cpu().numpy(), corners)
     want = at.area_normals(v, f)
-    got = _normals(_ctx(), v, f, offsets, corners)
+    got = _normals(h.ctx(), v, f, offsets, corners)
     valence = at.valence(f, len(v))
     print("%s: %d vertices, %d faces, valence %d..%d, %d zero normals"
           % (name, len(v), len(f), valence.min(), valence.max(), (want == 0).all(1).sum()))
@@ -251,7 +240,7 @@ def test_area_normals_are_the_restatement_bit_for_bit(meshes, name):
 
 
 def test_unused_vertices_and_bad_indices_are_skipped_and_harm_nothing():
-    ctx = _ctx()
+    ctx = h.ctx()
     v, f = at.tetrahedron()
     v5 = np.concatenate([v, [[9, 9, 9]]]).astype(F)
     offsets, corners = at.corner_table(f, 5)
@@ -289,13 +278,13 @@ def test_bad_arguments_are_refused_before_any_launch():
     import torch
     from raynet_amd import _lib
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     last = ctx.lib.rn_last_error
     null = ctypes.c_void_p(0)
     INVALID = -1
     v, f = at.tetrahedron()
     offsets, corners = at.corner_table(f, 4)
-    dv, df, do, dc = _cuda(v), _cuda(f), _cuda(offsets), _cuda(corners)
+    dv, df, do, dc = h.cuda(v), h.cuda(f), h.cuda(offsets), h.cuda(corners)
     out = torch.full((4, 3), -7.0, dtype=torch.float32, device="cuda")
     good = [4, _ptr(dv), 4, _ptr(df), _ptr(do), _ptr(dc), _ptr(out)]
     for at_, value in [(0, -1), (2, -1), (1, null), (3, null), (4, null), (5, null), (6, null),
@@ -307,7 +296,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     assert ctx.lib.rn_vertex_area_normals(ctx._h, 0, null, 0, null, null, null, null,
                                           _stream()) == _lib.RN_OK
     points, normals, cameras, images, depths = _scene(2, 24, 32, 3, seed=1)
-    dp, dn, dcam, dimg, ddep = [_cuda(a) for a in (points, normals, cameras, images, depths)]
+    dp, dn, dcam, dimg, ddep = [h.cuda(a) for a in (points, normals, cameras, images, depths)]
     colors = torch.full((300, 3), -7.0, dtype=torch.float32, device="cuda")
     weight = torch.full((300,), -7.0, dtype=torch.float32, device="cuda")
     views = torch.full((300,), -7, dtype=torch.int32, device="cuda")

@@ -7,13 +7,13 @@ labels in place of the GPU's, and the flags of the two mesh-writing scripts."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import components_truth as ct
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 CSRC = os.path.join(REPO, "raynet_amd", "csrc")
@@ -22,14 +22,7 @@ CSRC = os.path.join(REPO, "raynet_amd", "csrc")
 @pytest.mark.parametrize("sanitizers", [["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
                                         ["-fsanitize=thread"]], ids=["asan-ubsan", "tsan"])
 def test_checks_and_union_find_under_sanitizers(tmp_path, sanitizers):
-    exe = str(tmp_path / "components_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-pthread"] + sanitizers +
-                          ["-I", CSRC, os.path.join(REPO, "tests", "components_args_main.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("components_args: ok"), r.stdout
+    run_host_program("components", tmp_path, sanitizers, extra=["-pthread"])
 
 
 def _kernel(code, name):

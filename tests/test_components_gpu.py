@@ -13,46 +13,44 @@ import numpy as np
 import pytest
 
 import components_truth as ct
+import mesh_harness as h
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 D = np.float64
-PAD = 5
 FILL = -7
-
-
-def _ctx():
-    from raynet_amd.hip_implementations import get_context
-    return get_context()
 
 
 def _launch(faces, nv, counts=True, status=True):
     """rn_mesh_components on device tensors, the outputs PAD entries longer than nv and prefilled
-    -> (rc, labels, vertex_counts, face_counts, status) as host arrays, pads included."""
+    -> (rc, labels, vertex_counts, face_counts, status) as host arrays, pads included, and faces
+    on the device."""
     import torch
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
-    f = torch.from_numpy(np.ascontiguousarray(faces, np.int32).reshape(-1, 3)).cuda()
-    outs = [torch.full((nv + PAD,), FILL, dtype=torch.int32, device="cuda") for _ in range(3)]
-    word = torch.full((1 + PAD,), FILL, dtype=torch.int32, device="cuda")
+    ctx = h.ctx()
+    f = h.cuda(np.reshape(faces, (-1, 3)), np.int32)
+    outs = [h.padded(nv, FILL, torch.int32) for _ in range(3)]
+    word = h.padded(1, FILL, torch.int32)
     rc = ctx.lib.rn_mesh_components(ctx._h, nv, len(f), _ptr(f), _ptr(outs[0]),
                                     _ptr(outs[1] if counts else None),
                                     _ptr(outs[2] if counts else None),
                                     _ptr(word if status else None), _stream())
     torch.cuda.synchronize()
-    return (rc,) + tuple(o.cpu().numpy() for o in outs) + (word.cpu().numpy(),)
+    return (rc,) + tuple(o.cpu().numpy() for o in outs) + (word.cpu().numpy(), f)
 
 
 def _same_as_truth(faces, nv, what, want=None):
-    """The three arrays equal the truth's, the entries behind them keep their prefill, status 0."""
+    """The three arrays equal the truth's, the entries behind them keep their prefill, faces is
+    what it was, status 0."""
     from raynet_amd import _lib
     want = ct.components(faces, nv) if want is None else want
-    rc, labels, vc, fc, word = _launch(faces, nv)
+    rc, labels, vc, fc, word, f_after = _launch(faces, nv)
     assert rc == _lib.RN_OK, what
     for got, name in ((labels, "labels"), (vc, "vertex_counts"), (fc, "face_counts")):
-        assert (got[nv:] == FILL).all(), (what, name, "written beyond nv")
-    assert (word[1:] == FILL).all(), (what, "written beyond the status word")
+        h.assert_untouched(got, nv, FILL, (what, name))
+    h.assert_untouched(word, 1, FILL, (what, "the status word"))
+    h.assert_input_kept(f_after, np.reshape(faces, (-1, 3)), (what, "faces"))
     if nv == 0:
         assert word[0] == FILL, what                # no launch: nothing is written at all
     else:
@@ -167,10 +165,10 @@ def test_counts_and_status_are_optional():
     from raynet_amd import _lib
     faces, nv = ct.tetrahedra(100)
     want = ct.components(faces, nv)
-    rc, labels, vc, fc, word = _launch(faces, nv, counts=False, status=False)
+    rc, labels, vc, fc, word = _launch(faces, nv, counts=False, status=False)[:5]
     assert rc == _lib.RN_OK and np.array_equal(labels[:nv], want[0])
     assert (vc == FILL).all() and (fc == FILL).all() and (word == FILL).all()
-    rc, labels, vc, fc, word = _launch(faces, nv, counts=True, status=False)
+    rc, labels, vc, fc, word = _launch(faces, nv, counts=True, status=False)[:5]
     assert rc == _lib.RN_OK and np.array_equal(vc[:nv], want[1]) and np.array_equal(fc[:nv], want[2])
     assert (word == FILL).all()
 
@@ -219,7 +217,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     import torch
     from raynet_amd import _lib
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     last = ctx.lib.rn_last_error
     null = ctypes.c_void_p(0)
     INVALID = -1
@@ -264,49 +262,17 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------ d. the chain
-def _write_scene(path, bbox, cameras, H, W, gt_maps):
-    """A Restrepo scene directory of the given box, cameras (as text) and ground-truth depth
-    maps, with grey images."""
-    from PIL import Image as PILImage
-    for d in ("imgs", "cams_krt", "gt"):
-        os.makedirs(os.path.join(path, d))
-    with open(os.path.join(path, "scene_info.xml"), "w") as f:
-        f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                '  <bbox minx="%.9g" miny="%.9g" minz="%.9g" maxx="%.9g" maxy="%.9g" maxz="%.9g">\n'
-                '  </bbox>\n</bwm_info_for_boxm2>\n' % tuple(float(b) for b in bbox))
-    for i, (cam, depth) in enumerate(zip(cameras, gt_maps)):
-        PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-            os.path.join(path, "imgs", "frame_%03d.png" % i))
-        with open(os.path.join(path, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-            for row in np.asarray(cam.K, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n")
-            for row in np.asarray(cam.R, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, D).ravel()) + "\n")
-        np.save(os.path.join(path, "gt", "gt_depth_%d.npy" % i), depth)
-
-
 def test_from_ground_truth_maps_of_two_spheres_to_a_mesh_without_floaters(tmp_path, capsys):
-    import fusion_truth as ft
     from raynet_amd.common.mesh_io import parse_stl_file_to_pointcloud
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
     from raynet_amd.pointcloud import Pointcloud
     from raynet_amd.scripts import compute_metrics, fuse_depth_maps
-    from raynet_amd.synthetic import ring_cameras
     from raynet_amd.volume import SurfaceMesh
-    H, W, grid = 20, 30, (18, 22, 14)
-    bbox = np.array([-1, -1, -1, 1, 1, 1], F)
-    big, small = ((0.0, 0.0, -0.1), 0.5), ((-0.6, 0.55, 0.5), 0.15)
-    # (their surfaces are 0.36 apart, the truncation below is 0.25)
-    cams = ring_cameras(3, H, W, focal=1.5 * H)
-    gt_maps = []
-    for cam in cams:
-        d = np.minimum(ft.sphere_depth(cam, H, W, *big), ft.sphere_depth(cam, H, W, *small))
-        gt_maps.append(np.where(np.isfinite(d), d, F(0)).astype(F))
+    # (the spheres' surfaces are 0.36 apart, the truncation below is 0.25)
+    bbox, cams, H, W, grid, big, small, gt_maps = h.two_sphere_maps()
     scene_dir, preds = str(tmp_path / "scene"), str(tmp_path / "predictions")
-    _write_scene(scene_dir, bbox, cams, H, W, gt_maps)
+    h.write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
     os.makedirs(preds)
     on_disk = get_scene("restrepo", scene_dir)
     common = ["--gt", "--truncation", "0.25", "--start_end", "0,3", "--grid_shape", "18,22,14"]

@@ -6,27 +6,20 @@ truth's cleaning, and the flags of the fuse_depth_maps script."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fusion_truth as ft
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 CSRC = os.path.join(REPO, "raynet_amd", "csrc")
 
 
 def test_launcher_checks_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "fusion_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", CSRC, os.path.join(REPO, "tests", "fusion_args_main.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("fusion_args: ok"), r.stdout
+    run_host_program("fusion", tmp_path)
 
 
 def test_the_launcher_and_the_kernel_use_these_checks():

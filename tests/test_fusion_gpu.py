@@ -11,18 +11,13 @@ import numpy as np
 import pytest
 
 import fusion_truth as ft
+from mesh_harness import PAD, cuda, write_restrepo_scene
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 D = np.float64
-PAD = 5
 BBOX = np.array([-1.0, -1.2, -0.9, 1.1, 1.0, 1.3], F)
-
-
-def _cuda(a, dtype=None):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _ctx(grid, bbox=BBOX):
@@ -90,7 +85,7 @@ def test_the_volume_is_the_restatement_bit_for_bit(grid, V, HW):
     ctx = _ctx(grid)
     axes = ft.axes_of(BBOX, grid)
     cameras, depths, weights = _scene(V, H, W, seed=1000 * len(GRIDS) + 100 * V + 10 * H + grid[2])
-    d_cameras, d_depths, d_weights = _cuda(cameras), _cuda(depths), _cuda(weights)
+    d_cameras, d_depths, d_weights = cuda(cameras), cuda(depths), cuda(weights)
     if V == 0:
         d_cameras = d_depths = d_weights = None
     observed = 0
@@ -173,7 +168,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     null = ctypes.c_void_p(0)
     INVALID = -1
     cameras, depths, weights = _scene(2, 24, 32, seed=1)
-    dcam, ddep, dwei = _cuda(cameras), _cuda(depths), _cuda(weights)
+    dcam, ddep, dwei = cuda(cameras), cuda(depths), cuda(weights)
     tsdf = torch.full((ctx.G,), -7.0, dtype=torch.float32, device="cuda")
     weight = torch.full((ctx.G,), -7.0, dtype=torch.float32, device="cuda")
     #       0  1           2   3   4           5           6    7    8           9
@@ -216,29 +211,6 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------ d. the chain
-def _write_scene(path, bbox, cameras, H, W, gt_maps):
-    """A Restrepo scene directory of the given box, cameras (as text) and ground-truth depth
-    maps, with grey images."""
-    from PIL import Image as PILImage
-    for d in ("imgs", "cams_krt", "gt"):
-        os.makedirs(os.path.join(path, d))
-    with open(os.path.join(path, "scene_info.xml"), "w") as f:
-        f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                '  <bbox minx="%.9g" miny="%.9g" minz="%.9g" maxx="%.9g" maxy="%.9g" maxz="%.9g">\n'
-                '  </bbox>\n</bwm_info_for_boxm2>\n' % tuple(float(b) for b in bbox))
-    for i, (cam, depth) in enumerate(zip(cameras, gt_maps)):
-        PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-            os.path.join(path, "imgs", "frame_%03d.png" % i))
-        with open(os.path.join(path, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-            for row in np.asarray(cam.K, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n")
-            for row in np.asarray(cam.R, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, D).ravel()) + "\n")
-        np.save(os.path.join(path, "gt", "gt_depth_%d.npy" % i), depth)
-
-
 def test_from_a_forward_pass_to_a_fused_mesh_its_file_and_the_metrics(tmp_path):
     from raynet_amd.common.generation_parameters import GenerationParameters
     from raynet_amd.common.mesh_io import parse_gt_data_from_ply, parse_stl_file_to_pointcloud
@@ -294,7 +266,7 @@ def test_from_a_forward_pass_to_a_fused_mesh_its_file_and_the_metrics(tmp_path):
     for cam in cams:
         d = ft.sphere_depth(cam, H, W, (0.0, 0.0, -0.1), 0.5)
         gt_maps.append(np.where(np.isfinite(d), d, F(0)).astype(F))
-    _write_scene(scene_dir, bbox, cams, H, W, gt_maps)
+    write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
     os.makedirs(preds)
     for i in range(3):
         np.save(os.path.join(preds, "depth_%03d.npy" % i), maps[i])

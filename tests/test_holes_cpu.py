@@ -8,27 +8,20 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import holes_truth as ht
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 CSRC = os.path.join(REPO, "raynet_amd", "csrc")
 
 
 def test_checks_layout_and_phases_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "holes_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I", CSRC,
-                           os.path.join(REPO, "tests", "holes_args_main.cpp"), "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("holes_args: ok"), r.stdout
+    run_host_program("holes", tmp_path)
 
 
 def test_the_launcher_and_the_kernels_use_the_header():

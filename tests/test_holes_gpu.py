@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import holes_truth as ht
+import mesh_harness as h
 import smooth_truth as st
 
 pytestmark = pytest.mark.gpu
@@ -21,47 +22,42 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 D = np.float64
 I = np.int32
-PAD = 5                 # rows behind every output
-TAIL = 64               # bytes behind the workspace
 FILL = -7.5
 INVALID = -1
-
-
-def _ctx():
-    from raynet_amd.hip_implementations import get_context
-    return get_context()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def _launch(vertices, faces, offsets, corners, max_edges):
     """rn_mesh_fill_holes on device tensors, every output PAD rows longer than its bound and the
     workspace TAIL bytes longer than reported, all prefilled -> (rc, new_vertices, new_faces,
-    source, counts, the four inputs afterwards, the workspace's tail)."""
+    source, counts, the four inputs on the device, the workspace, the bytes it needs)."""
     import torch
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     nv, nf = len(vertices), len(faces)
-    v = torch.from_numpy(np.ascontiguousarray(vertices, F).reshape(-1, 3)).cuda()
-    f = torch.from_numpy(np.ascontiguousarray(faces, I).reshape(-1, 3)).cuda()
-    o = torch.from_numpy(np.ascontiguousarray(offsets, I)).cuda()
-    c = torch.from_numpy(np.ascontiguousarray(corners, I)).cuda()
+    v, f = h.cuda(np.reshape(vertices, (-1, 3)), F), h.cuda(np.reshape(faces, (-1, 3)), I)
+    o, c = h.cuda(offsets, I), h.cuda(corners, I)
     need = int(ctx.lib.rn_mesh_fill_holes_workspace_bytes(nv, nf))
     assert need >= 32 * nv + 3 * nf + 16 and need % 8 == 0
-    work = torch.full((need + TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
-    nvo = torch.full((nf + PAD, 3), FILL, dtype=torch.float32, device="cuda")
-    nfo = torch.full((3 * nf + PAD, 3), -77, dtype=torch.int32, device="cuda")
-    so = torch.full((nf + PAD,), -77, dtype=torch.int32, device="cuda")
-    counts = torch.full((5 + PAD,), -77, dtype=torch.int64, device="cuda")
+    work = h.workspace(need)
+    nvo = h.padded((nf, 3), FILL, torch.float32)
+    nfo = h.padded((3 * nf, 3), -77, torch.int32)
+    so = h.padded(nf, -77, torch.int32)
+    counts = h.padded(5, -77, torch.int64)
     rc = ctx.lib.rn_mesh_fill_holes(ctx._h, nv, _ptr(v), nf, _ptr(f), _ptr(o), _ptr(c), int(max_edges),
                                     _ptr(nvo), _ptr(nfo), _ptr(so), _ptr(counts), _ptr(work),
                                     _stream())
     torch.cuda.synchronize()
     return (rc, nvo.cpu().numpy(), nfo.cpu().numpy(), so.cpu().numpy(), counts.cpu().numpy(),
-            (v.cpu().numpy(), f.cpu().numpy(), o.cpu().numpy(), c.cpu().numpy()),
-            work[need:].cpu().numpy())
+            (v, f, o, c), work, need)
+
+
+def _untouched(nvo, nfo, so, counts, work, need, k, m, what):
+    """Nothing behind the k new vertices, the m new faces, the five counts and the workspace."""
+    h.assert_untouched(counts, 5, -77, (what, "counts"))
+    h.assert_untouched(nvo, k, FILL, (what, "new_vertices"))
+    h.assert_untouched(nfo, m, -77, (what, "new_faces"))
+    h.assert_untouched(so, k, -77, (what, "source"))
+    h.assert_untouched(work, need, h.TAIL_BYTE, (what, "the workspace"))
 
 
 def _same_as_truth(vertices, faces, max_edges, what, want=None):
@@ -73,22 +69,17 @@ def _same_as_truth(vertices, faces, max_edges, what, want=None):
     offsets, corners = ht.corner_table(faces, len(vertices))
     if want is None:
         want = ht.fill(vertices, faces, max_edges)
-    rc, nvo, nfo, so, counts, after, tail = _launch(vertices, faces, offsets, corners, max_edges)
+    rc, nvo, nfo, so, counts, after, work, need = _launch(vertices, faces, offsets, corners,
+                                                          max_edges)
     assert rc == _lib.RN_OK, what
     k, m = len(want[0]), len(want[1])
     print("%s: nv %d, nf %d, max_edges %d: counts %s (truth %s)"
           % (what, len(vertices), len(faces), max_edges, counts[:5].tolist(), want[3].tolist()))
     assert counts[:5].tolist() == want[3].tolist(), (what, counts[:5], want[3])
-    assert (counts[5:] == -77).all(), what
-    assert (_bits(nvo[k:]) == _bits(F(FILL))).all(), (what, "rows behind counts[0] were written")
-    assert (nfo[m:] == -77).all() and (so[k:] == -77).all(), (what, "rows behind the counts")
-    assert (tail == 0xA5).all(), (what, "behind the workspace")
-    assert np.array_equal(_bits(after[0]), _bits(vertices)), (what, "vertices was written")
-    assert np.array_equal(after[1], faces), (what, "faces was written")
-    assert np.array_equal(after[2], offsets) and np.array_equal(after[3], corners), what
-    differ = (_bits(nvo[:k]) != _bits(want[0])).any(1)
-    assert not differ.any(), (what, int(differ.sum()), np.flatnonzero(differ)[:5],
-                              nvo[:k][differ][:3], want[0][differ][:3])
+    _untouched(nvo, nfo, so, counts, work, need, k, m, what)
+    for tensor, uploaded in zip(after, (vertices, faces, offsets, corners)):
+        h.assert_input_kept(tensor, uploaded, what)
+    h.assert_same_bits(nvo[:k], want[0], what)
     assert np.array_equal(nfo[:m], want[1]), what
     assert np.array_equal(so[:k], want[2]), what
     return want
@@ -110,7 +101,7 @@ def test_every_mesh_of_the_truth(name):
 def test_the_properties_hold_on_the_gpus_result():
     from raynet_amd.smoothing import boundary_vertices
     vertices, faces = ht.tube(300)
-    ctx = _ctx()
+    ctx = h.ctx()
     import torch
     from raynet_amd.appearance import corner_table
     v, f = torch.from_numpy(vertices).cuda(), torch.from_numpy(faces).cuda()
@@ -158,9 +149,9 @@ def test_three_launches_give_one_result(large):
     vertices, faces, want = large
     offsets, corners = ht.corner_table(faces, len(vertices))
     for _ in range(3):
-        rc, nvo, nfo, so, counts, _, _ = _launch(vertices, faces, offsets, corners, 16)
+        rc, nvo, nfo, so, counts = _launch(vertices, faces, offsets, corners, 16)[:5]
         assert rc == 0 and counts[:5].tolist() == want[3].tolist()
-        assert np.array_equal(_bits(nvo[:49]), _bits(want[0])) and np.array_equal(nfo[:196], want[1])
+        assert np.array_equal(h.bits(nvo[:49]), h.bits(want[0])) and np.array_equal(nfo[:196], want[1])
 
 
 def test_a_corner_table_that_is_not_the_meshs_reads_nothing_out_of_bounds():
@@ -176,11 +167,12 @@ def test_a_corner_table_that_is_not_the_meshs_reads_nothing_out_of_bounds():
     off[hit] = rng.choice(junk, int(hit.sum()))
     hit = rng.random(len(cor)) < 0.1
     cor[hit] = rng.choice(junk, int(hit.sum()))
-    rc, nvo, nfo, so, counts, _, tail = _launch(vertices, faces, off.astype(I), cor.astype(I), 10)
-    assert rc == _lib.RN_OK and (tail == 0xA5).all() and (counts[5:] == -77).all()
+    rc, nvo, nfo, so, counts, _, work, need = _launch(vertices, faces, off.astype(I),
+                                                      cor.astype(I), 10)
+    assert rc == _lib.RN_OK
     k, m = int(counts[0]), int(counts[1])
     assert 0 <= k <= len(faces) and 0 <= m <= 3 * len(faces) and m <= counts[4] <= 3 * len(faces)
-    assert (_bits(nvo[k:]) == _bits(F(FILL))).all() and (nfo[m:] == -77).all() and (so[k:] == -77).all()
+    _untouched(nvo, nfo, so, counts, work, need, k, m, "a table that is not the mesh's")
     assert ((nfo[:m] >= 0) & (nfo[:m] < len(vertices) + k)).all()
 
 
@@ -189,7 +181,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     import torch
     from raynet_amd import _lib
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     vertices, faces = ht.punched_sheet()
     nv, nf = len(vertices), len(faces)
     offsets, corners = ht.corner_table(faces, nv)
@@ -228,9 +220,9 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert b"rn_mesh_fill_holes" in ctx.lib.rn_last_error(ctx._h), change
     assert ctx.lib.rn_mesh_fill_holes(None, *good.values(), _stream()) == INVALID
     torch.cuda.synchronize()
-    assert (_bits(nvo.cpu().numpy()) == _bits(F(FILL))).all() and (nfo == -77).all()
+    assert (h.bits(nvo.cpu().numpy()) == h.bits(F(FILL))).all() and (nfo == -77).all()
     assert (so == -77).all() and (counts == -77).all() and (work == 0xA5).all()
-    assert np.array_equal(_bits(v.cpu().numpy()), _bits(vertices)) and np.array_equal(f.cpu().numpy(), faces)
+    assert np.array_equal(h.bits(v.cpu().numpy()), h.bits(vertices)) and np.array_equal(f.cpu().numpy(), faces)
     assert ctx.lib.rn_mesh_fill_holes_workspace_bytes(-1, 0) == -1
     assert ctx.lib.rn_mesh_fill_holes_workspace_bytes(0, 2 ** 40) == -1
     assert ctx.lib.rn_mesh_fill_holes_workspace_bytes(2 ** 31 - 1, 0) == -1
@@ -264,65 +256,25 @@ def test_fill_holes_and_surface_mesh_filled_are_the_truth():
     vertices, faces = ht.punched_sheet()
     want = ht.filled_mesh(vertices, faces, 10)
     got = fill_holes(vertices, faces, 10)
-    assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(got[1], want[1])
+    assert np.array_equal(h.bits(got[0]), h.bits(want[0])) and np.array_equal(got[1], want[1])
     assert np.array_equal(got[2], want[2]) and got[3] == want[3]
     colors = np.random.default_rng(2).integers(0, 256, size=(len(vertices), 3)).astype(np.uint8)
     mesh = SurfaceMesh(vertices, faces, colors=colors)
     mesh.compute_normals()
     out = mesh.filled(10)
-    assert np.array_equal(_bits(out.vertices), _bits(want[0])) and np.array_equal(out.faces, want[1])
+    assert np.array_equal(h.bits(out.vertices), h.bits(want[0])) and np.array_equal(out.faces, want[1])
     assert np.array_equal(out.colors[len(vertices):], colors[want[2]])
     assert out.normals.shape == out.vertices.shape and (out.normals[len(vertices):, 2] > 0).all()
 
 
 # ------------------------------------------------------------------------------ d. the chain
-NOISE_SIGMA, NOISE_SEED = 0.02, 0       # the scene of tests/test_smooth_gpu.py
-PATCH = (slice(9, 11), slice(14, 16))   # blanked in every view: chosen on the CPU with the truths
-
-
-def _write_scene(path, bbox, cameras, H, W, gt_maps):
-    """A Restrepo scene directory of the given box, cameras (as text) and ground-truth depth
-    maps, with grey images."""
-    from PIL import Image as PILImage
-    for d in ("imgs", "cams_krt", "gt"):
-        os.makedirs(os.path.join(path, d))
-    with open(os.path.join(path, "scene_info.xml"), "w") as f:
-        f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                '  <bbox minx="%.9g" miny="%.9g" minz="%.9g" maxx="%.9g" maxy="%.9g" maxz="%.9g">\n'
-                '  </bbox>\n</bwm_info_for_boxm2>\n' % tuple(float(b) for b in bbox))
-    for i, (cam, depth) in enumerate(zip(cameras, gt_maps)):
-        PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-            os.path.join(path, "imgs", "frame_%03d.png" % i))
-        with open(os.path.join(path, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-            for row in np.asarray(cam.K, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n")
-            for row in np.asarray(cam.R, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, D).ravel()) + "\n")
-        np.save(os.path.join(path, "gt", "gt_depth_%d.npy" % i), depth)
-
-
 def test_from_maps_with_a_blanked_patch_to_a_mesh_without_the_patchs_loops(tmp_path, capsys):
-    import fusion_truth as ft
     from raynet_amd.scripts import fuse_depth_maps
-    from raynet_amd.synthetic import ring_cameras
     from raynet_amd.volume import SurfaceMesh
-    H, W, grid = 20, 30, (18, 22, 14)
-    bbox = np.array([-1, -1, -1, 1, 1, 1], F)
-    big, small = ((0.0, 0.0, -0.1), 0.5), ((-0.6, 0.55, 0.5), 0.15)
-    cams = ring_cameras(3, H, W, focal=1.5 * H)
-    rng = np.random.default_rng(NOISE_SEED)
-    gt_maps = []
-    for cam in cams:
-        d = np.minimum(ft.sphere_depth(cam, H, W, *big), ft.sphere_depth(cam, H, W, *small))
-        d = np.where(np.isfinite(d), d, F(0)).astype(F)
-        d = np.where(d > 0, d + rng.normal(scale=NOISE_SIGMA, size=d.shape).astype(F), F(0)).astype(F)
-        assert (d[PATCH] > 0).all()
-        d[PATCH] = 0
-        gt_maps.append(d)
+    bbox, cams, H, W, grid, big, small, gt_maps = h.two_sphere_maps(h.NOISE_SIGMA, h.NOISE_SEED,
+                                                                    blank=h.PATCH)
     scene_dir, preds = str(tmp_path / "scene"), str(tmp_path / "predictions")
-    _write_scene(scene_dir, bbox, cams, H, W, gt_maps)
+    h.write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
     os.makedirs(preds)
     common = ["--gt", "--truncation", "0.25", "--start_end", "0,3", "--grid_shape", "18,22,14",
               "--keep_largest", "1", "--normals"]
@@ -339,7 +291,7 @@ def test_from_maps_with_a_blanked_patch_to_a_mesh_without_the_patchs_loops(tmp_p
     border = st.boundary_vertices(faces, len(vertices))
     want = st.smooth(vertices, faces, 5, 0.5, -0.53, border, side)
     assert np.array_equal(after.faces, faces)
-    assert np.array_equal(_bits(after.vertices), _bits(want))
+    assert np.array_equal(h.bits(after.vertices), h.bits(want))
     # the printed line
     longer = stats["loops"] - stats["filled"] - stats["not_simple"]
     line = "holes: %d loops, %d filled (%d not simple, %d longer than 40), %d -> %d faces" % (
@@ -349,7 +301,7 @@ def test_from_maps_with_a_blanked_patch_to_a_mesh_without_the_patchs_loops(tmp_p
     # the patch's loops -- short and simple, where the ragged rim of the three views' caps is
     # neither -- are gone from the boundary; the rim is as it was
     assert stats["filled"] >= 2 and stats["loops"] > stats["filled"], stats
-    h, a, b = ht.boundary_half_edges(before.faces, len(before.vertices))
+    _, a, b = ht.boundary_half_edges(before.faces, len(before.vertices))
     label = ht.loop_labels(a, b, len(before.vertices))
     on_filled = np.isin(label[a], source)
     was = st.boundary_vertices(before.faces, len(before.vertices))

@@ -13,6 +13,7 @@ import pytest
 
 import isosurface_truth as it
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 
@@ -78,14 +79,7 @@ def test_the_table_in_the_kernel_file_is_the_derived_one():
 
 
 def test_launcher_arithmetic_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "isosurface_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(REPO, "raynet_amd", "csrc"),
-                           os.path.join(REPO, "tests", "isosurface_args_main.cpp"), "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("isosurface_args: ok"), r.stdout
+    run_host_program("isosurface", tmp_path)
 
 
 # ------------------------------------------------------------------------- SurfaceMesh

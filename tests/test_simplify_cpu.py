@@ -8,7 +8,6 @@ mesh-writing scripts."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,20 +16,14 @@ import components_truth as ct
 import simplify_truth as sp
 import smooth_truth as st
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 CSRC = os.path.join(REPO, "raynet_amd", "csrc")
 
 
 def test_checks_layout_and_phases_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "simplify_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I", CSRC,
-                           os.path.join(REPO, "tests", "simplify_args_main.cpp"), "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("simplify_args: ok"), r.stdout
+    run_host_program("simplify", tmp_path)
 
 
 def test_the_launcher_and_the_kernels_use_the_header():

@@ -17,6 +17,7 @@ import pytest
 
 import components_truth as ct
 import isosurface_truth as it
+import mesh_harness as h
 import simplify_truth as sp
 import smooth_truth as st
 
@@ -25,19 +26,8 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 D = np.float64
 I = np.int32
-PAD = 5                 # rows behind every output
-TAIL = 64               # bytes behind the workspace
 FILL = -7.5
 NO_FACES = np.zeros((0, 3), I)
-
-
-def _ctx():
-    from raynet_amd.hip_implementations import get_context
-    return get_context()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def _host3(values, ctype):
@@ -48,29 +38,28 @@ def _host3(values, ctype):
 def _launch(vertices, faces, origin, cell, dims):
     """rn_mesh_simplify on device tensors, every output PAD rows longer than its bound and the
     workspace TAIL bytes longer than reported, all prefilled -> (rc, vertices_out, faces_out,
-    source, cluster, counts, vertices_in and faces_in afterwards, the workspace's tail)."""
+    source, cluster, counts, vertices_in and faces_in on the device, the workspace, the bytes it
+    needs)."""
     import torch
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     nv, nf = len(vertices), len(faces)
-    v = torch.from_numpy(np.ascontiguousarray(vertices, F).reshape(-1, 3)).cuda()
-    f = torch.from_numpy(np.ascontiguousarray(faces, I).reshape(-1, 3)).cuda()
+    v, f = h.cuda(np.reshape(vertices, (-1, 3)), F), h.cuda(np.reshape(faces, (-1, 3)), I)
     d = _host3(dims, ctypes.c_int32)
     need = int(ctx.lib.rn_mesh_simplify_workspace_bytes(nv, nf, d))
     cells = int(np.prod(np.asarray(dims, np.int64)))
     assert need >= 32 * cells + 8 * nf + 12 * nv and need % 8 == 0
-    work = torch.full((need + TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
-    vo = torch.full((nv + PAD, 3), FILL, dtype=torch.float32, device="cuda")
-    fo = torch.full((nf + PAD, 3), -77, dtype=torch.int32, device="cuda")
-    so = torch.full((nv + PAD,), -77, dtype=torch.int32, device="cuda")
-    cl = torch.full((nv + PAD,), -77, dtype=torch.int32, device="cuda")
-    counts = torch.full((2 + PAD,), -77, dtype=torch.int64, device="cuda")
+    work = h.workspace(need)
+    vo = h.padded((nv, 3), FILL, torch.float32)
+    fo = h.padded((nf, 3), -77, torch.int32)
+    so, cl = h.padded(nv, -77, torch.int32), h.padded(nv, -77, torch.int32)
+    counts = h.padded(2, -77, torch.int64)
     rc = ctx.lib.rn_mesh_simplify(ctx._h, nv, _ptr(v), nf, _ptr(f), _host3(origin, ctypes.c_double),
                                   _host3(cell, ctypes.c_double), d, _ptr(vo), _ptr(fo), _ptr(so),
                                   _ptr(cl), _ptr(counts), _ptr(work), _stream())
     torch.cuda.synchronize()
     return (rc, vo.cpu().numpy(), fo.cpu().numpy(), so.cpu().numpy(), cl.cpu().numpy(),
-            counts.cpu().numpy(), v.cpu().numpy(), f.cpu().numpy(), work[need:].cpu().numpy())
+            counts.cpu().numpy(), v, f, work, need)
 
 
 def _same_as_truth(vertices, faces, grid, what, want=None):
@@ -79,23 +68,24 @@ def _same_as_truth(vertices, faces, grid, what, want=None):
     from raynet_amd import _lib
     vertices = np.ascontiguousarray(vertices, F).reshape(-1, 3)
     faces = np.ascontiguousarray(faces, I).reshape(-1, 3)
-    nv, nf = len(vertices), len(faces)
+    nv = len(vertices)
     origin, cell, dims = grid
     if want is None:
         want = sp.simplify(vertices, faces, origin, cell, dims)
-    rc, vo, fo, so, cl, counts, v_after, f_after, tail = _launch(vertices, faces, origin, cell, dims)
+    rc, vo, fo, so, cl, counts, v_after, f_after, work, need = _launch(vertices, faces, origin,
+                                                                       cell, dims)
     assert rc == _lib.RN_OK, what
     nvo, nfo = len(want[0]), len(want[1])
     assert counts[:2].tolist() == [nvo, nfo], (what, counts[:2], nvo, nfo)
-    assert (counts[2:] == -77).all(), what
-    assert (_bits(vo[nvo:]) == _bits(F(FILL))).all(), (what, "rows behind nv_out were written")
-    assert (fo[nfo:] == -77).all() and (so[nvo:] == -77).all(), (what, "rows behind the counts")
-    assert (cl[nv:] == -77).all() and (tail == 0xA5).all(), (what, "behind cluster / the workspace")
-    assert np.array_equal(_bits(v_after), _bits(vertices)), (what, "vertices_in was written")
-    assert np.array_equal(f_after, faces), (what, "faces_in was written")
-    differ = (_bits(vo[:nvo]) != _bits(want[0])).any(1)
-    assert not differ.any(), (what, int(differ.sum()), np.flatnonzero(differ)[:5],
-                              vo[:nvo][differ][:3], want[0][differ][:3])
+    h.assert_untouched(counts, 2, -77, (what, "counts"))
+    h.assert_untouched(vo, nvo, FILL, (what, "vertices_out"))
+    h.assert_untouched(fo, nfo, -77, (what, "faces_out"))
+    h.assert_untouched(so, nvo, -77, (what, "source"))
+    h.assert_untouched(cl, nv, -77, (what, "cluster"))
+    h.assert_untouched(work, need, h.TAIL_BYTE, (what, "the workspace"))
+    h.assert_input_kept(v_after, vertices, (what, "vertices_in"))
+    h.assert_input_kept(f_after, faces, (what, "faces_in"))
+    h.assert_same_bits(vo[:nvo], want[0], what)
     assert np.array_equal(fo[:nfo], want[1]), what
     assert np.array_equal(so[:nvo], want[2]), what
     assert np.array_equal(cl[:nv], want[3]), what
@@ -131,7 +121,7 @@ def test_one_triangle_in_one_cell_vanishes_and_in_three_survives():
     gone = _same_as_truth(tri, face, UNIT, "one cell")
     assert len(gone[0]) == 0 and len(gone[1]) == 0
     kept = _same_as_truth(tri, face, (np.zeros(3), np.full(3, 0.5), np.array([2, 2, 2], I)), "three")
-    assert np.array_equal(_bits(kept[0]), _bits(tri)) and np.array_equal(kept[1], face)
+    assert np.array_equal(h.bits(kept[0]), h.bits(tri)) and np.array_equal(kept[1], face)
 
 
 def test_one_tetrahedron():
@@ -173,7 +163,7 @@ def test_five_thousand_vertices_in_one_cell_and_in_five_thousand():
     assert kept[2].tolist() == [0, 5000, 5001] and kept[1].tolist() == [[0, 1, 2]]
     vertices, faces = sp.spread_cloud(5000, seed=3)
     alone = _same_as_truth(vertices, faces, sp.grid_around(vertices, 1.0), "5000 cells")
-    assert np.array_equal(_bits(alone[0]), _bits(vertices))
+    assert np.array_equal(h.bits(alone[0]), h.bits(vertices))
 
 
 # ------------------------------------------------------------------------------ b. surfaces
@@ -197,7 +187,7 @@ def test_the_wrapper_and_the_mesh_method_on_the_ball(ball):
     want = sp.simplify(vertices, faces, *sp.grid_around(vertices, 2.0))
     want_faces = sp.unique_faces(want[1])[0]
     out, out_faces, source = simplify_mesh(vertices, faces, 2.0)
-    assert np.array_equal(_bits(out), _bits(want[0])) and np.array_equal(out_faces, want_faces)
+    assert np.array_equal(h.bits(out), h.bits(want[0])) and np.array_equal(out_faces, want_faces)
     assert np.array_equal(source, want[2])
     assert np.array_equal(simplify_mesh(vertices, faces, 2.0, drop_duplicate_faces=False)[1], want[1])
     rng = np.random.default_rng(4)
@@ -205,10 +195,10 @@ def test_the_wrapper_and_the_mesh_method_on_the_ball(ball):
     mesh = SurfaceMesh(vertices, faces, colors=colors)
     mesh.compute_normals()
     small = mesh.simplified(2.0)
-    assert np.array_equal(_bits(small.vertices), _bits(want[0]))
+    assert np.array_equal(h.bits(small.vertices), h.bits(want[0]))
     assert np.array_equal(small.faces, want_faces) and np.array_equal(small.colors, colors[want[2]])
-    assert np.array_equal(_bits(small.normals),
-                          _bits(SurfaceMesh(want[0], want_faces).compute_normals()))
+    assert np.array_equal(h.bits(small.normals),
+                          h.bits(SurfaceMesh(want[0], want_faces).compute_normals()))
     assert SurfaceMesh(vertices, faces).simplified(2.0).normals is None
     smooth = small.smoothed(iterations=5)
     assert np.isfinite(smooth.vertices).all() and np.array_equal(smooth.faces, small.faces)
@@ -246,7 +236,7 @@ def test_garbage_in_the_faces_and_the_positions_reads_nothing_out_of_bounds(ball
     # (no operation of the definition makes a NaN that is stored: a singleton keeps its own bits)
     for i in (100, 200, 300):
         if got[3][i] >= 0:
-            assert np.array_equal(_bits(got[0][got[3][i]]), _bits(bad[i]))
+            assert np.array_equal(h.bits(got[0][got[3][i]]), h.bits(bad[i]))
     nothing = np.full_like(vertices, np.nan)
     got = _same_as_truth(nothing, faces, grid, "all NaN")
     assert len(got[0]) == len(vertices) and np.array_equal(got[1], faces)
@@ -266,7 +256,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     from raynet_amd import _lib
     from raynet_amd.hip_implementations.context import _ptr, _stream
     from raynet_amd.simplify import simplify_mesh
-    ctx = _ctx()
+    ctx = h.ctx()
     last = ctx.lib.rn_last_error
     null = ctypes.c_void_p(0)
     INVALID = -1
@@ -318,7 +308,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     torch.cuda.synchronize()
     assert (vo == FILL).all() and (work == 0xA5).all() and (fo == -77).all()
     assert (so == -77).all() and (cl == -77).all() and (counts == -77).all()
-    assert np.array_equal(_bits(v.cpu().numpy()), _bits(vertices_np))
+    assert np.array_equal(h.bits(v.cpu().numpy()), h.bits(vertices_np))
     # what is NOT refused: no faces and no pointers to them; nothing at all; source and cluster
     # not wanted; the limits of the sizes (the size entry: nothing that large is allocated here)
     assert ctx.lib.rn_mesh_simplify(ctx._h, nv, _ptr(v), 0, null, o, c, d, _ptr(vo), null, _ptr(so),
@@ -392,53 +382,18 @@ def test_unique_faces_on_the_device_is_the_dictionarys(ball):
 
 
 # ------------------------------------------------------------------------------ e. the chain
-def _write_scene(path, bbox, cameras, H, W, gt_maps):
-    """A Restrepo scene directory of the given box, cameras (as text) and ground-truth depth
-    maps, with grey images."""
-    from PIL import Image as PILImage
-    for d in ("imgs", "cams_krt", "gt"):
-        os.makedirs(os.path.join(path, d))
-    with open(os.path.join(path, "scene_info.xml"), "w") as f:
-        f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                '  <bbox minx="%.9g" miny="%.9g" minz="%.9g" maxx="%.9g" maxy="%.9g" maxz="%.9g">\n'
-                '  </bbox>\n</bwm_info_for_boxm2>\n' % tuple(float(b) for b in bbox))
-    for i, (cam, depth) in enumerate(zip(cameras, gt_maps)):
-        PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-            os.path.join(path, "imgs", "frame_%03d.png" % i))
-        with open(os.path.join(path, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-            for row in np.asarray(cam.K, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n")
-            for row in np.asarray(cam.R, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, D).ravel()) + "\n")
-        np.save(os.path.join(path, "gt", "gt_depth_%d.npy" % i), depth)
-
-
 def test_from_the_maps_of_two_spheres_to_a_simplified_smoothed_mesh(tmp_path, capsys):
     """Section 23's scene through fuse_depth_maps --gt --keep_largest 1 --simplify 2 --smooth 5
     --normals; the run without --simplify is the yardstick, a run without --smooth either gives
     the mesh both start from."""
-    import fusion_truth as ft
     from raynet_amd.common.mesh_io import parse_stl_file_to_pointcloud
     from raynet_amd.common.scene import get_scene
     from raynet_amd.pointcloud import Pointcloud
     from raynet_amd.scripts import compute_metrics, fuse_depth_maps
-    from raynet_amd.synthetic import ring_cameras
     from raynet_amd.volume import SurfaceMesh
-    H, W, grid = 20, 30, (18, 22, 14)
-    bbox = np.array([-1, -1, -1, 1, 1, 1], F)
-    big, small = ((0.0, 0.0, -0.1), 0.5), ((-0.6, 0.55, 0.5), 0.15)
-    cams = ring_cameras(3, H, W, focal=1.5 * H)
-    rng = np.random.default_rng(0)
-    gt_maps = []
-    for cam in cams:
-        d = np.minimum(ft.sphere_depth(cam, H, W, *big), ft.sphere_depth(cam, H, W, *small))
-        d = np.where(np.isfinite(d), d, F(0)).astype(F)
-        gt_maps.append(np.where(d > 0, d + rng.normal(scale=0.02, size=d.shape).astype(F),
-                                F(0)).astype(F))
+    bbox, cams, H, W, grid, big, small, gt_maps = h.two_sphere_maps(h.NOISE_SIGMA, h.NOISE_SEED)
     scene_dir, preds = str(tmp_path / "scene"), str(tmp_path / "predictions")
-    _write_scene(scene_dir, bbox, cams, H, W, gt_maps)
+    h.write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
     os.makedirs(preds)
     on_disk = get_scene("restrepo", scene_dir)
     common = ["--gt", "--truncation", "0.25", "--start_end", "0,3", "--grid_shape", "18,22,14",
@@ -468,7 +423,7 @@ def test_from_the_maps_of_two_spheres_to_a_simplified_smoothed_mesh(tmp_path, ca
     border = st.boundary_vertices(want_faces, len(want[0]))
     smooth = st.smooth(want[0], want_faces, 5, 0.5, -0.53, border, float(voxel.min()))
     assert np.array_equal(got.faces, want_faces)
-    assert np.array_equal(_bits(got.vertices), _bits(smooth))
+    assert np.array_equal(h.bits(got.vertices), h.bits(smooth))
     assert got.normals is not None and np.isfinite(got.normals).all()
     # the printed counts are the file's, and the faces are fewer than the yardstick's
     m = re.search(r"^simplify: cell 2 voxel sides, (\d+) -> (\d+) vertices, (\d+) -> (\d+) faces$",

@@ -8,7 +8,6 @@ scripts."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import pytest
 import components_truth as ct
 import smooth_truth as st
 from conftest import REPO
+from host_program import run_host_program
 
 F = np.float32
 CSRC = os.path.join(REPO, "raynet_amd", "csrc")
@@ -26,14 +26,7 @@ def _bits(a):
 
 
 def test_checks_ring_and_steps_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "smooth_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", CSRC, os.path.join(REPO, "tests", "smooth_args_main.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("smooth_args: ok"), r.stdout
+    run_host_program("smooth", tmp_path)
 
 
 def test_the_launcher_and_the_kernels_use_the_header():

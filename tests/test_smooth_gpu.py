@@ -17,80 +17,56 @@ import pytest
 import appearance_truth as at
 import components_truth as ct
 import isosurface_truth as it
+import mesh_harness as h
 import smooth_truth as st
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 D = np.float64
-PAD = 5                 # rows behind vertices_out
-TAIL = 64               # bytes behind the workspace
 FILL = -7.5
 INF = float("inf")
 NO_FACES = np.zeros((0, 3), np.int32)
 
 
-def _ctx():
-    from raynet_amd.hip_implementations import get_context
-    return get_context()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
 def _launch(vertices, faces, offsets, corners, fixed, iterations, lam, mu, max_move):
     """rn_mesh_smooth on device tensors, the output PAD rows longer than nv and the workspace TAIL
-    bytes longer than reported, both prefilled -> (rc, out with its pad, vertices_in afterwards,
-    the workspace's tail) as host arrays."""
+    bytes longer than reported, both prefilled -> (rc, out with its pad, the four inputs
+    afterwards, the workspace, the bytes it needs)."""
     import torch
     from raynet_amd.hip_implementations.context import _ptr, _stream
-    ctx = _ctx()
+    ctx = h.ctx()
     nv, nf = len(vertices), len(faces)
-    v = torch.from_numpy(np.ascontiguousarray(vertices, F).reshape(-1, 3)).cuda()
-    f = torch.from_numpy(np.ascontiguousarray(faces, np.int32).reshape(-1, 3)).cuda()
-    o = torch.from_numpy(np.ascontiguousarray(offsets, np.int32)).cuda()
-    c = torch.from_numpy(np.ascontiguousarray(corners, np.int32)).cuda()
-    fx = None if fixed is None else torch.from_numpy(np.ascontiguousarray(fixed, np.uint8)).cuda()
+    v, f = h.cuda(np.reshape(vertices, (-1, 3)), F), h.cuda(np.reshape(faces, (-1, 3)), np.int32)
+    o, c, fx = h.cuda(offsets, np.int32), h.cuda(corners, np.int32), h.cuda(fixed, np.uint8)
     need = int(ctx.lib.rn_mesh_smooth_workspace_bytes(ctx._h, nv, nf))
     assert need == (24 * nf + 12 * nv + 7) // 8 * 8
-    work = torch.full((need + TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
-    out = torch.full((nv + PAD, 3), FILL, dtype=torch.float32, device="cuda")
+    work, out = h.workspace(need), h.padded((nv, 3), FILL, torch.float32)
     rc = ctx.lib.rn_mesh_smooth(ctx._h, nv, _ptr(v), nf, _ptr(f), _ptr(o), _ptr(c), _ptr(fx),
                                 int(iterations), float(lam), float(mu), float(max_move),
                                 _ptr(work), _ptr(out), _stream())
     torch.cuda.synchronize()
-    return rc, out.cpu().numpy(), v.cpu().numpy(), work[need:].cpu().numpy()
+    return rc, out.cpu().numpy(), (v, f, o, c), work, need
 
 
 def _same_as_truth(vertices, faces, what, iterations=10, lam=0.5, mu=-0.53, fixed=None,
                    max_move=INF, offsets=None, corners=None, nan_payloads=False):
-    """vertices_out has the truth's bits, vertices_in its own, the pads their prefill -> out."""
+    """vertices_out has the truth's bits, the inputs their own, the pads their prefill -> out."""
     from raynet_amd import _lib
     vertices = np.ascontiguousarray(vertices, F).reshape(-1, 3)
     nv = len(vertices)
     if offsets is None:
         offsets, corners = at.corner_table(faces, nv)
     want = st.smooth(vertices, faces, iterations, lam, mu, fixed, max_move, offsets, corners)
-    rc, out, after, tail = _launch(vertices, faces, offsets, corners, fixed, iterations, lam, mu,
-                                   max_move)
+    rc, out, after, work, need = _launch(vertices, faces, offsets, corners, fixed, iterations, lam,
+                                         mu, max_move)
     assert rc == _lib.RN_OK, what
-    assert (out[nv:] == F(FILL)).all(), (what, "rows behind vertices_out were written")
-    assert (tail == 0xA5).all(), (what, "bytes behind the workspace were written")
-    assert np.array_equal(_bits(after), _bits(vertices)), (what, "vertices_in was written")
-    got = out[:nv]
-    if nan_payloads:
-        # (a NaN that an operation makes -- inf - inf -- has the sign and payload of the machine
-        # that made it, which the definition does not fix: NaN where the truth has NaN, and the
-        # bits everywhere else)
-        both = np.isnan(got) & np.isnan(want)
-        assert np.array_equal(np.isnan(got), np.isnan(want)), what
-        assert np.array_equal(_bits(got)[~both], _bits(want)[~both]), what
-    else:
-        differ = (_bits(got) != _bits(want)).any(1)
-        assert not differ.any(), (what, int(differ.sum()), np.flatnonzero(differ)[:5],
-                                  got[differ][:3], want[differ][:3])
-    return got
+    h.assert_untouched(out, nv, FILL, (what, "vertices_out"))
+    h.assert_untouched(work, need, h.TAIL_BYTE, (what, "the workspace"))
+    for tensor, uploaded in zip(after, (vertices, np.reshape(faces, (-1, 3)), offsets, corners)):
+        h.assert_input_kept(tensor, uploaded, what)
+    h.assert_same_bits(out[:nv], want, what, nan_payloads)
+    return out[:nv]
 
 
 @pytest.fixture(scope="module")
@@ -116,9 +92,9 @@ def test_empty_and_trivial(faces, nv):
     vertices = st.positions(nv, seed=nv)
     out = _same_as_truth(vertices, faces, "trivial")
     if len(faces) == 0:
-        assert np.array_equal(_bits(out), _bits(vertices))
+        assert np.array_equal(h.bits(out), h.bits(vertices))
     else:
-        assert (_bits(out) != _bits(vertices)).any(1).all()
+        assert (h.bits(out) != h.bits(vertices)).any(1).all()
         _same_as_truth(vertices, faces, "trivial, 1 iteration", iterations=1)
         _same_as_truth(vertices, faces, "trivial, no iteration", iterations=0)
 
@@ -135,7 +111,7 @@ def test_one_long_row_among_short_ones(hub_last):
     vertices, faces = st.star(500, seed=5, hub_last=hub_last)
     out = _same_as_truth(vertices, faces, "star")
     hub = len(vertices) - 1 if hub_last else 0
-    assert (_bits(out[hub]) != _bits(vertices[hub])).any()
+    assert (h.bits(out[hub]) != h.bits(vertices[hub])).any()
 
 
 # ------------------------------------------------------------------------------ b. iso-surfaces
@@ -160,12 +136,12 @@ def test_the_open_iso_surface_of_the_cut_ball_with_its_border_pinned():
     want_border = st.boundary_vertices(faces, len(vertices))
     assert 0 < want_border.sum() < len(vertices) and np.array_equal(border, want_border)
     out = _same_as_truth(vertices, faces, "cut ball", fixed=want_border)
-    assert np.array_equal(_bits(out[want_border]), _bits(vertices[want_border]))
+    assert np.array_equal(h.bits(out[want_border]), h.bits(vertices[want_border]))
     # the wrapper pins the same vertices by itself
-    assert np.array_equal(_bits(smooth_vertices(vertices, faces, fixed="boundary")), _bits(out))
+    assert np.array_equal(h.bits(smooth_vertices(vertices, faces, fixed="boundary")), h.bits(out))
     free = smooth_vertices(vertices, faces, fixed=None)
-    assert np.array_equal(_bits(free), _bits(st.smooth(vertices, faces)))
-    assert (_bits(free[want_border]) != _bits(vertices[want_border])).any()
+    assert np.array_equal(h.bits(free), h.bits(st.smooth(vertices, faces)))
+    assert (h.bits(free[want_border]) != h.bits(vertices[want_border])).any()
 
 
 # ------------------------------------------------------------------ c. step counts and parameters
@@ -227,7 +203,7 @@ def test_garbage_in_all_three_index_arrays_reads_nothing_out_of_bounds(ball):
     p = st.positions(5, 27)
     out = _same_as_truth(p, only.astype(np.int32), "only garbage", offsets=[0, 4, 8, 8, 8, 8],
                          corners=[0, 3, 4, 7, 9, 10, 2, 5, 1, 6, 8, 11])
-    assert np.array_equal(_bits(out), _bits(p))
+    assert np.array_equal(h.bits(out), h.bits(p))
 
 
 def test_three_launches_give_one_array():
@@ -237,7 +213,7 @@ def test_three_launches_give_one_array():
     runs = [_launch(vertices, faces, offsets, corners, None, 10, 0.5, -0.53, INF) for _ in range(3)]
     for run in runs:
         assert run[0] == _lib.RN_OK
-        assert np.array_equal(_bits(run[1]), _bits(runs[0][1]))
+        assert np.array_equal(h.bits(run[1]), h.bits(runs[0][1]))
 
 
 # ------------------------------------------------------------------------------ d. refusals
@@ -246,7 +222,7 @@ def test_bad_arguments_are_refused_before_any_launch():
     from raynet_amd import _lib
     from raynet_amd.hip_implementations.context import _ptr, _stream
     from raynet_amd.smoothing import smooth_vertices
-    ctx = _ctx()
+    ctx = h.ctx()
     last = ctx.lib.rn_last_error
     null = ctypes.c_void_p(0)
     INVALID = -1
@@ -281,12 +257,12 @@ def test_bad_arguments_are_refused_before_any_launch():
     assert ctx.lib.rn_mesh_smooth_workspace_bytes(ctx._h, 2 ** 31 - 1, 0) == -1
     torch.cuda.synchronize()
     assert (out == FILL).all() and (work == 0xA5).all()
-    assert np.array_equal(_bits(v.cpu().numpy()), _bits(vertices_np))
+    assert np.array_equal(h.bits(v.cpu().numpy()), h.bits(vertices_np))
     # what is NOT refused: no faces and no pointers to them; nothing at all; the limits
     assert ctx.lib.rn_mesh_smooth(ctx._h, nv, _ptr(v), 0, null, _ptr(o), null, *good[6:],
                                   _stream()) == _lib.RN_OK
     torch.cuda.synchronize()
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(vertices_np))
+    assert np.array_equal(h.bits(out.cpu().numpy()), h.bits(vertices_np))
     assert ctx.lib.rn_mesh_smooth(ctx._h, 0, null, 0, null, null, null, null, 10, 0.5, -0.53, INF,
                                   null, null, _stream()) == _lib.RN_OK
     for where, value in [(7, 0), (8, 1.0), (9, -1.0), (9, 0.0), (10, 1e-300),
@@ -298,14 +274,14 @@ def test_bad_arguments_are_refused_before_any_launch():
     # the context method: what it returns, and tensors that are not what the kernels read
     got = ctx.mesh_smooth(v, f, o, c)
     assert got.dtype == torch.float32 and tuple(got.shape) == (nv, 3)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(st.smooth(vertices_np, faces_np)))
+    assert np.array_equal(h.bits(got.cpu().numpy()), h.bits(st.smooth(vertices_np, faces_np)))
     pins = torch.zeros((nv,), dtype=torch.uint8, device="cuda")
     pins[::4] = 1
     given = ctx.mesh_smooth(v, f, o, c, fixed=pins, iterations=3, lam=0.4, mu=-0.45, max_move=0.5,
                             workspace=work, out=out)
     assert given is out and np.array_equal(
-        _bits(out.cpu().numpy()),
-        _bits(st.smooth(vertices_np, faces_np, 3, 0.4, -0.45, pins.cpu().numpy(), 0.5)))
+        h.bits(out.cpu().numpy()),
+        h.bits(st.smooth(vertices_np, faces_np, 3, 0.4, -0.45, pins.cpu().numpy(), 0.5)))
     for bad, match in [
             (dict(vertices=v.double()), "vertices"), (dict(vertices=v.cpu()), "vertices"),
             (dict(faces=f.long()), "faces"), (dict(offsets=o[:-1]), "offsets"),
@@ -328,53 +304,15 @@ def test_bad_arguments_are_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------ e. the chain
-NOISE_SIGMA, NOISE_SEED = 0.02, 0       # chosen on the CPU with the restatements: DESIGN.md 23
-
-
-def _write_scene(path, bbox, cameras, H, W, gt_maps):
-    """A Restrepo scene directory of the given box, cameras (as text) and ground-truth depth
-    maps, with grey images."""
-    from PIL import Image as PILImage
-    for d in ("imgs", "cams_krt", "gt"):
-        os.makedirs(os.path.join(path, d))
-    with open(os.path.join(path, "scene_info.xml"), "w") as f:
-        f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                '  <bbox minx="%.9g" miny="%.9g" minz="%.9g" maxx="%.9g" maxy="%.9g" maxz="%.9g">\n'
-                '  </bbox>\n</bwm_info_for_boxm2>\n' % tuple(float(b) for b in bbox))
-    for i, (cam, depth) in enumerate(zip(cameras, gt_maps)):
-        PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-            os.path.join(path, "imgs", "frame_%03d.png" % i))
-        with open(os.path.join(path, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-            for row in np.asarray(cam.K, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n")
-            for row in np.asarray(cam.R, D):
-                f.write(" ".join("%.9g" % x for x in row) + "\n")
-            f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, D).ravel()) + "\n")
-        np.save(os.path.join(path, "gt", "gt_depth_%d.npy" % i), depth)
-
-
 def test_from_noisy_maps_of_two_spheres_to_a_smoother_mesh(tmp_path, capsys):
-    import fusion_truth as ft
     from raynet_amd.common.mesh_io import parse_stl_file_to_pointcloud
     from raynet_amd.common.scene import get_scene
     from raynet_amd.pointcloud import Pointcloud
     from raynet_amd.scripts import compute_metrics, fuse_depth_maps
-    from raynet_amd.synthetic import ring_cameras
     from raynet_amd.volume import SurfaceMesh
-    H, W, grid = 20, 30, (18, 22, 14)
-    bbox = np.array([-1, -1, -1, 1, 1, 1], F)
-    big, small = ((0.0, 0.0, -0.1), 0.5), ((-0.6, 0.55, 0.5), 0.15)
-    cams = ring_cameras(3, H, W, focal=1.5 * H)
-    rng = np.random.default_rng(NOISE_SEED)
-    gt_maps = []
-    for cam in cams:
-        d = np.minimum(ft.sphere_depth(cam, H, W, *big), ft.sphere_depth(cam, H, W, *small))
-        d = np.where(np.isfinite(d), d, F(0)).astype(F)
-        gt_maps.append(np.where(d > 0, d + rng.normal(scale=NOISE_SIGMA, size=d.shape).astype(F),
-                                F(0)).astype(F))
+    bbox, cams, H, W, grid, big, small, gt_maps = h.two_sphere_maps(h.NOISE_SIGMA, h.NOISE_SEED)
     scene_dir, preds = str(tmp_path / "scene"), str(tmp_path / "predictions")
-    _write_scene(scene_dir, bbox, cams, H, W, gt_maps)
+    h.write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
     os.makedirs(preds)
     on_disk = get_scene("restrepo", scene_dir)
     common = ["--gt", "--truncation", "0.25", "--start_end", "0,3", "--grid_shape", "18,22,14",
@@ -393,7 +331,7 @@ def test_from_noisy_maps_of_two_spheres_to_a_smoother_mesh(tmp_path, capsys):
     side = float((2.0 / np.array(grid, D)).min())
     border = st.boundary_vertices(rough.faces, len(rough.vertices))
     want = st.smooth(rough.vertices, rough.faces, 5, 0.5, -0.53, border, side)
-    assert np.array_equal(_bits(smooth.vertices), _bits(want))
+    assert np.array_equal(h.bits(smooth.vertices), h.bits(want))
     # the printed line, and the farthest move within the default limit
     m = re.search(r"^smooth: 5 iterations, (\d+) vertices, farthest move ([0-9.]+) voxel sides$",
                   printed, re.M)

@@ -3,20 +3,12 @@
 undefined-behaviour sanitizers: tests/volume_args_main.cpp, compiled with g++ and run here --
 no GPU, no HIP, nothing loaded into this interpreter."""
 import os
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_program import REPO, run_host_program
 
 
 def test_launcher_argument_checks_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "volume_args")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(REPO, "raynet_amd", "csrc"),
-                           os.path.join(REPO, "tests", "volume_args_main.cpp"), "-o", exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert r.stdout.strip().endswith("volume_args: ok"), r.stdout
+    run_host_program("volume", tmp_path)
 
 
 def test_the_launchers_use_these_checks():

@@ -8,17 +8,9 @@
 
 #include "../include/raynet_hip.h"
 #include "raynet_volume_args.h"
+#include "host_main.h"
 
 using namespace rn_volume;
-
-static int failures = 0;
-#define EXPECT(cond)                                                     \
-    do {                                                                 \
-        if (!(cond)) {                                                   \
-            std::printf("line %d: expected %s\n", __LINE__, #cond);      \
-            failures++;                                                  \
-        }                                                                \
-    } while (0)
 
 // what an entry returns for a verdict, before it launches anything
 static int status(Verdict v) { return v == INVALID ? RN_ERR_INVALID : RN_OK; }
@@ -69,7 +61,5 @@ int main() {
     }
     // no 32-bit overflow in between: the last float of 2^31 - 1 rays at the same stride
     EXPECT(out_index(4, 0x7fffffffLL, 0x7ffffffe) == (size_t)4 * 0x7fffffffULL + 0x7ffffffeULL);
-    if (failures) return 1;
-    std::printf("volume_args: ok\n");
-    return 0;
+    return finish("volume");
 }

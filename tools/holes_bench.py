@@ -28,22 +28,17 @@ their own:
 --trace runs nothing but the warm-ups and repeats of the entry; --merge_trace and --merge_box (no
 GPU) add the kernels' own times and the box's speed to the JSON.
 """
-import argparse
-import csv
 import json
 import os
 import sys
 import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mesh_bench as mb  # noqa: E402  (puts the repository on the path)
 
 import numpy as np  # noqa: E402
 
-sys.path.insert(0, os.path.join(REPO, "tools"))
-from simplify_bench import meshes, stats  # noqa: E402  (the two meshes of sections 23 and 24)
-
-MESHES = ("mrf_128", "fused_256")
+MESHES = mb.MESHES
 MAX_EDGES = (16, 64, 1024)
 OWN = ("k_holes_init", "k_holes_edges", "k_holes_flatten", "k_holes_tally", "k_holes_flags",
        "k_holes_emit")
@@ -62,43 +57,20 @@ def loop_lengths(ctx, vertices, faces, offsets, corners):
 def two_sphere_chain():
     """surface_completeness of the two-sphere chain with the stage and without it."""
     import torch  # noqa: F401
-    from PIL import Image as PILImage
     from raynet_amd.common.scene import get_scene
     from raynet_amd.metrics import SurfaceCompleteness
     from raynet_amd.scripts import fuse_depth_maps
-    from raynet_amd.synthetic import ring_cameras
     from raynet_amd.volume import SurfaceMesh
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    import fusion_truth as ft
-    F, H, W, grid = np.float32, 20, 30, (18, 22, 14)
-    big, small = ((0.0, 0.0, -0.1), 0.5), ((-0.6, 0.55, 0.5), 0.15)
-    cams = ring_cameras(3, H, W, focal=1.5 * H)
-    rng = np.random.default_rng(0)
+    sys.path.insert(0, os.path.join(mb.REPO, "tests"))
+    import mesh_harness as h
+    F = np.float32
+    bbox, cams, H, W, grid, big, small, gt_maps = h.two_sphere_maps(h.NOISE_SIGMA, h.NOISE_SEED,
+                                                                    blank=h.PATCH)
     out = {"patch": "rows 9:11, columns 14:16 of every view", "max_edges": 40, "samples": 2000}
     with tempfile.TemporaryDirectory() as tmp:
         scene_dir, preds = os.path.join(tmp, "scene"), os.path.join(tmp, "predictions")
-        for d in ("imgs", "cams_krt", "gt"):
-            os.makedirs(os.path.join(scene_dir, d))
+        h.write_restrepo_scene(scene_dir, bbox, cams, H, W, gt_maps)
         os.makedirs(preds)
-        with open(os.path.join(scene_dir, "scene_info.xml"), "w") as f:
-            f.write('<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n<bwm_info_for_boxm2>\n'
-                    '  <bbox minx="-1" miny="-1" minz="-1" maxx="1" maxy="1" maxz="1">\n'
-                    '  </bbox>\n</bwm_info_for_boxm2>\n')
-        for i, cam in enumerate(cams):
-            d = np.minimum(ft.sphere_depth(cam, H, W, *big), ft.sphere_depth(cam, H, W, *small))
-            d = np.where(np.isfinite(d), d, F(0)).astype(F)
-            d = np.where(d > 0, d + rng.normal(scale=0.02, size=d.shape).astype(F), F(0)).astype(F)
-            d[9:11, 14:16] = 0
-            np.save(os.path.join(scene_dir, "gt", "gt_depth_%d.npy" % i), d)
-            PILImage.fromarray(np.full((H, W, 3), 40 * i + 60, np.uint8)).save(
-                os.path.join(scene_dir, "imgs", "frame_%03d.png" % i))
-            with open(os.path.join(scene_dir, "cams_krt", "frame_%03d.txt" % i), "w") as f:
-                for row in np.asarray(cam.K, np.float64):
-                    f.write(" ".join("%.9g" % x for x in row) + "\n")
-                f.write("\n")
-                for row in np.asarray(cam.R, np.float64):
-                    f.write(" ".join("%.9g" % x for x in row) + "\n")
-                f.write("\n" + " ".join("%.9g" % x for x in np.asarray(cam.t, np.float64).ravel()) + "\n")
         # the ground truth: the large sphere as a latitude-longitude mesh
         n_lat, n_lon = 48, 96
         lat = np.pi * (np.arange(n_lat + 1) / n_lat)
@@ -134,7 +106,7 @@ def measure(args):
     from raynet_amd.hip_implementations import get_context
     from raynet_amd.hip_implementations.context import _ptr, _stream
     _lib.build()
-    found = meshes()
+    found = mb.bench_meshes()
     ctx = get_context()
     res = {"tool": "holes_bench", "device": torch.cuda.get_device_name(0),
            "version": _lib.load().rn_version().decode(), "repeats": args.repeats,
@@ -174,20 +146,14 @@ def measure(args):
             }
             if args.trace:
                 launches = {"fill_holes": launches["fill_holes"]}
-            ms = {k: [] for k in launches}
-            for i in range(args.warmup + args.repeats):
-                for k, f in launches.items():
-                    ctx.timer_start()
-                    f()
-                    ms[k].append(ctx.timer_stop())
-            torch.cuda.synchronize()
+            ms = mb.take_turns(ctx, launches, args.warmup, args.repeats)
             if args.trace:
                 continue
             got = counts.tolist()
             one = {"filled": got[0], "new_faces": got[1],
                    "longest_filled": int(lengths[lengths <= max_edges][-1]) if (lengths <= max_edges).any() else 0}
             for k in launches:
-                one[k] = stats(ms[k][args.warmup:])
+                one[k] = mb.stats(ms[k])
             one["fill_holes"]["ratio_to_components"] = round(
                 one["fill_holes"]["ms_median"] / one["components"]["ms_median"], 3)
             entry["max_edges"]["%d" % max_edges] = one
@@ -195,11 +161,7 @@ def measure(args):
     if args.trace:
         return
     res["two_sphere_chain_surface_completeness"] = two_sphere_chain()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    mb.write_record(res, args.out)
 
 
 def merge_trace(args):
@@ -208,62 +170,17 @@ def merge_trace(args):
     run, in the order of the meshes and of max_edges."""
     res = json.loads(open(args.out).read())
     turns = res["warmup"] + res["repeats"]
-    rows = {k: [] for k in OWN}
-    with open(args.merge_trace) as f:
-        for row in csv.DictReader(f):
-            for k in OWN:
-                if k in row["Kernel_Name"]:
-                    rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
     plan = [(name, "%d" % m) for name in MESHES for m in res["max_edges"]]
-    for k in OWN:
-        rows[k].sort()
-        if len(rows[k]) < len(plan) * turns:
-            raise SystemExit("%s: %d dispatches in the trace, expected %d"
-                             % (k, len(rows[k]), len(plan) * turns))
-        rows[k] = rows[k][-len(plan) * turns:]
+    rows = mb.keep_last(mb.trace_rows(args.merge_trace, OWN), {k: len(plan) * turns for k in OWN})
     for at, (name, m) in enumerate(plan):
         own = {}
         for k in OWN:
             mine = rows[k][at * turns:(at + 1) * turns][res["warmup"]:]
-            own[k] = stats([(e - s) * 1e-6 for s, e in mine])
+            own[k] = mb.stats([(e - s) * 1e-6 for s, e in mine])
         own["sum_of_own_kernels_ms"] = round(sum(own[k]["ms_median"] for k in OWN), 4)
         res["meshes"][name]["max_edges"][m]["kernel_trace"] = own
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def merge_box(args):
-    """bench.py's JSON line of the same visit, under "box"."""
-    res = json.loads(open(args.out).read())
-    lines = [l for l in open(args.merge_box).read().splitlines() if l.strip().startswith("{")]
-    res["box"] = json.loads(lines[-1])
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--trace", action="store_true",
-                    help="only the entry's launches (for a kernel trace); writes nothing")
-    ap.add_argument("--merge_trace", default=None,
-                    help="a rocprofv3 kernel_trace.csv of --trace: add the kernels' times (no GPU)")
-    ap.add_argument("--merge_box", default=None,
-                    help="a file with bench.py's JSON line of the same visit (no GPU)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "holes_bench.json"))
-    args = ap.parse_args()
-    if args.merge_trace:
-        merge_trace(args)
-    elif args.merge_box:
-        merge_box(args)
-    else:
-        measure(args)
+    mb.write_record(res, args.out)
 
 
 if __name__ == "__main__":
-    main()
+    mb.main("holes_bench", measure, merge_trace)

@@ -34,56 +34,21 @@ their own:
 --trace runs nothing but the warm-ups and repeats of the entry; --merge_trace and --merge_box (no
 GPU) add the kernels' own times and the box's speed to the JSON.
 """
-import argparse
-import csv
 import ctypes
 import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mesh_bench as mb  # noqa: E402  (puts the repository on the path)
 
 import numpy as np  # noqa: E402
 
-H, W, V, NEIGHBORS, D, M = 480, 640, 5, 4, 64, 384
-GRID, FUSED_GRID, THRESHOLD = (128, 128, 128), (256, 256, 128), 0.5
-MESHES = ("mrf_128", "fused_256")
+MESHES = mb.MESHES
 CELLS = (2.0, 4.0)
 SMOOTH_ITERATIONS = 10
 OWN = ("k_simplify_clear", "k_simplify_bin", "k_simplify_face_flags", "k_simplify_emit_vertices",
        "k_simplify_emit_faces")
-
-
-def meshes():
-    """-> {name: (vertices (nv, 3) f32 device, faces (nf, 3) i32 device, the voxel's sides [3])}."""
-    import torch
-    from raynet_amd.common.generation_parameters import GenerationParameters
-    from raynet_amd.forward_pass import get_forward_pass_factory
-    from raynet_amd.fusion import fuse_scene
-    from raynet_amd.synthetic import make_synthetic_scene
-    scene, bank = make_synthetic_scene(H=H, W=W, n_views=V, focal=1.5 * H, seed=1234)
-    gp = GenerationParameters(depth_planes=D, neighbors=NEIGHBORS,
-                              grid_shape=np.array(GRID, np.int32),
-                              max_number_of_marched_voxels=M, padding=11, gamma_mrf=0.05)
-    fp = get_forward_pass_factory("raynet")(bank, gp, "sample_in_bbox", (H, W), 0)
-    pairs = [(np.array(m), np.array(s.confidence))
-             for m, s in fp.forward_pass(scene, (0, V, 1), with_statistics=True)]
-    mrf = fp.occupancy_volume()
-    fused = fuse_scene(scene, [m for m, _ in pairs], range(V), FUSED_GRID,
-                       weights=[c for _, c in pairs])
-    out = {}
-    for name, volume, mesh in (("mrf_128", mrf, mrf.mesh(THRESHOLD)),
-                               ("fused_256", fused, fused.mesh())):
-        bbox = np.asarray(volume.bbox, np.float64)
-        voxel = (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
-        out[name] = (torch.from_numpy(np.ascontiguousarray(mesh.vertices)).cuda(),
-                     torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int32)).cuda(), voxel)
-    return out
-
-
-def stats(ms):
-    return {"ms_min": round(float(min(ms)), 4), "ms_median": round(float(np.median(ms)), 4)}
 
 
 def scan_launches(n):
@@ -114,13 +79,10 @@ def time_smoothing(ctx, vertices, faces, args):
     work = torch.empty((max(ctx.mesh_smooth_workspace_bytes(nv, nf), 8),), dtype=torch.uint8,
                        device="cuda")
     out = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
-    ms = []
-    for i in range(args.warmup + args.repeats):
-        ctx.timer_start()
-        ctx.mesh_smooth(vertices, faces, offsets, corners, fixed, SMOOTH_ITERATIONS, 0.5, -0.53,
-                        float("inf"), work, out)
-        ms.append(ctx.timer_stop())
-    return stats(ms[args.warmup:])
+    ms = mb.take_turns(ctx, {"smooth": lambda: ctx.mesh_smooth(
+        vertices, faces, offsets, corners, fixed, SMOOTH_ITERATIONS, 0.5, -0.53, float("inf"), work,
+        out)}, args.warmup, args.repeats)
+    return mb.stats(ms["smooth"])
 
 
 def measure(args):
@@ -130,7 +92,7 @@ def measure(args):
     from raynet_amd.hip_implementations.context import _ptr, _stream
     from raynet_amd.simplify import cluster_grid, unique_faces
     _lib.build()
-    found = meshes()
+    found = mb.bench_meshes()
     ctx = get_context()
     res = {"tool": "simplify_bench", "device": torch.cuda.get_device_name(0),
            "version": _lib.load().rn_version().decode(), "repeats": args.repeats,
@@ -166,13 +128,7 @@ def measure(args):
             }
             if args.trace:
                 del launches["components"]
-            ms = {k: [] for k in launches}
-            for i in range(args.warmup + args.repeats):
-                for k, f in launches.items():
-                    ctx.timer_start()
-                    f()
-                    ms[k].append(ctx.timer_stop())
-            torch.cuda.synchronize()
+            ms = mb.take_turns(ctx, launches, args.warmup, args.repeats)
             if args.trace:
                 continue
             nvo, nfo = (int(x) for x in counts.tolist())
@@ -185,7 +141,7 @@ def measure(args):
                    "vertex_reduction": round(nv / max(nvo, 1), 2),
                    "bytes_must_move": per_kernel}
             for k in launches:
-                one[k] = stats(ms[k][args.warmup:])
+                one[k] = mb.stats(ms[k])
             one["simplify"]["GB_per_s"] = round(total / (one["simplify"]["ms_median"] * 1e-3) / 1e9, 1)
             one["simplify"]["ratio_to_components"] = round(
                 one["simplify"]["ms_median"] / one["components"]["ms_median"], 3)
@@ -201,11 +157,7 @@ def measure(args):
         res["meshes"][name] = entry
     if args.trace:
         return
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    mb.write_record(res, args.out)
 
 
 def merge_trace(args):
@@ -213,14 +165,7 @@ def merge_trace(args):
     res = json.loads(open(args.out).read())
     turns = res["warmup"] + res["repeats"]
     names = OWN + ("k_scan_reduce", "k_scan_tile")
-    rows = {k: [] for k in names}
-    with open(args.merge_trace) as f:
-        for row in csv.DictReader(f):
-            for k in names:
-                if k in row["Kernel_Name"]:
-                    rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
-    for k in names:
-        rows[k].sort()
+    rows = mb.trace_rows(args.merge_trace, names)
     at = {k: 0 for k in names}
     # the turns are the last dispatches of the run (the scan also serves the meshes' extraction,
     # which came before): walk backwards from the end of every kernel's list
@@ -232,11 +177,7 @@ def merge_trace(args):
             per_turn = {k: 1 for k in OWN}
             per_turn.update(k_scan_reduce=reduce_n, k_scan_tile=tile_n)
             plan.append((name, "%g" % cell, per_turn))
-    for k in names:
-        expected = sum(p[2][k] for p in plan) * turns
-        if len(rows[k]) < expected:
-            raise SystemExit("%s: %d dispatches in the trace, expected %d" % (k, len(rows[k]), expected))
-        rows[k] = rows[k][-expected:]
+    mb.keep_last(rows, {k: sum(p[2][k] for p in plan) * turns for k in names})
     for name, cell, per_turn in plan:
         own = {}
         one = res["meshes"][name]["cells"][cell]
@@ -245,7 +186,7 @@ def merge_trace(args):
             mine = rows[k][at[k]:at[k] + p * turns]
             at[k] += p * turns
             sums = [sum((e - s) * 1e-6 for s, e in mine[i * p:(i + 1) * p]) for i in range(turns)]
-            own[k] = stats(sums[res["warmup"]:])
+            own[k] = mb.stats(sums[res["warmup"]:])
             own[k]["launches"] = p
         scans = own["k_scan_reduce"]["ms_median"] + own["k_scan_tile"]["ms_median"]
         own["scans"] = {"ms_median": round(scans, 4)}
@@ -253,42 +194,8 @@ def merge_trace(args):
             own[k]["GB_per_s"] = round(one["bytes_must_move"][k] / (own[k]["ms_median"] * 1e-3) / 1e9, 1)
         own["sum_of_kernels_ms"] = round(sum(own[k]["ms_median"] for k in OWN) + scans, 4)
         one["kernel_trace"] = own
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def merge_box(args):
-    """bench.py's JSON line of the same visit, under "box"."""
-    res = json.loads(open(args.out).read())
-    lines = [l for l in open(args.merge_box).read().splitlines() if l.strip().startswith("{")]
-    res["box"] = json.loads(lines[-1])
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--trace", action="store_true",
-                    help="only the entry's launches (for a kernel trace); writes nothing")
-    ap.add_argument("--merge_trace", default=None,
-                    help="a rocprofv3 kernel_trace.csv of --trace: add the kernels' times (no GPU)")
-    ap.add_argument("--merge_box", default=None,
-                    help="a file with bench.py's JSON line of the same visit (no GPU)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "simplify_bench.json"))
-    args = ap.parse_args()
-    if args.merge_trace:
-        merge_trace(args)
-    elif args.merge_box:
-        merge_box(args)
-    else:
-        measure(args)
+    mb.write_record(res, args.out)
 
 
 if __name__ == "__main__":
-    main()
+    mb.main("simplify_bench", measure, merge_trace)

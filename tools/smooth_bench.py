@@ -25,49 +25,20 @@ kernel trace of their own, with the normals launch beside them:
 --trace runs nothing but the meshes' warm-ups and repeats; --merge_trace and --merge_box (no GPU)
 add the kernels' own times per mesh, the two ratios of section 23, and the box's speed to the JSON.
 """
-import argparse
-import csv
 import json
 import os
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mesh_bench as mb  # noqa: E402  (puts the repository on the path)
 
 import numpy as np  # noqa: E402
 
-H, W, V, NEIGHBORS, D, M = 480, 640, 5, 4, 64, 384
-GRID, FUSED_GRID, THRESHOLD = (128, 128, 128), (256, 256, 128), 0.5
-MESHES = ("mrf_128", "fused_256")
+MESHES = mb.MESHES
 ITERATIONS, LAMBDA, MU = 10, 0.5, -0.53
 STEPS = 2 * ITERATIONS
 KERNELS = {"k_smooth_ring": 1, "k_smooth_step": STEPS, "k_vertex_area_normals": 1}   # per turn
-
-
-def meshes():
-    """-> {name: (vertices (nv, 3) f32 device, faces (nf, 3) i32 device)}."""
-    import torch
-    from raynet_amd.common.generation_parameters import GenerationParameters
-    from raynet_amd.forward_pass import get_forward_pass_factory
-    from raynet_amd.fusion import fuse_scene
-    from raynet_amd.synthetic import make_synthetic_scene
-    scene, bank = make_synthetic_scene(H=H, W=W, n_views=V, focal=1.5 * H, seed=1234)
-    gp = GenerationParameters(depth_planes=D, neighbors=NEIGHBORS,
-                              grid_shape=np.array(GRID, np.int32),
-                              max_number_of_marched_voxels=M, padding=11, gamma_mrf=0.05)
-    fp = get_forward_pass_factory("raynet")(bank, gp, "sample_in_bbox", (H, W), 0)
-    pairs = [(np.array(m), np.array(s.confidence))
-             for m, s in fp.forward_pass(scene, (0, V, 1), with_statistics=True)]
-    out = {}
-    mrf = fp.occupancy_volume().mesh(THRESHOLD)
-    out["mrf_128"] = (mrf.vertices, mrf.faces)
-    fused = fuse_scene(scene, [m for m, _ in pairs], range(V), FUSED_GRID,
-                       weights=[c for _, c in pairs]).mesh()
-    out["fused_256"] = (fused.vertices, fused.faces)
-    return {k: (torch.from_numpy(np.ascontiguousarray(v)).cuda(),
-                torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32)).cuda())
-            for k, (v, f) in out.items()}
 
 
 def host_smooth(vertices, faces, fixed):
@@ -91,10 +62,6 @@ def host_smooth(vertices, faces, fixed):
     return time.perf_counter() - t0, now
 
 
-def stats(ms):
-    return {"ms_min": round(float(min(ms)), 4), "ms_median": round(float(np.median(ms)), 4)}
-
-
 def measure(args):
     import torch
     from raynet_amd import _lib
@@ -102,14 +69,14 @@ def measure(args):
     from raynet_amd.hip_implementations import get_context
     from raynet_amd.smoothing import boundary_vertices
     _lib.build()
-    found = meshes()
+    found = mb.bench_meshes()
     ctx = get_context()
     res = {"tool": "smooth_bench", "device": torch.cuda.get_device_name(0),
            "version": _lib.load().rn_version().decode(), "repeats": args.repeats,
            "warmup": args.warmup, "iterations": ITERATIONS, "lambda": LAMBDA, "mu": MU,
            "meshes": {}}
     for name in MESHES:
-        vertices, faces = found[name]
+        vertices, faces, _ = found[name]
         nv, nf = len(vertices), len(faces)
         offsets, corners = corner_table(faces, nv)
         border = boundary_vertices(faces, nv)
@@ -124,17 +91,7 @@ def measure(args):
             "normals_alone": lambda: ctx.vertex_area_normals(vertices, faces, offsets, corners,
                                                              normals),
         }
-        for _ in range(args.warmup):
-            for f in launches.values():
-                f()
-        torch.cuda.synchronize()
-        ms = {k: [] for k in launches}
-        for _ in range(args.repeats):
-            for k, f in launches.items():
-                ctx.timer_start()
-                f()
-                ms[k].append(ctx.timer_stop())
-        torch.cuda.synchronize()
+        ms = mb.take_turns(ctx, launches, args.warmup, args.repeats)
         if args.trace:
             continue
         step_bytes = 24 * nv + 12 * nv + 24 * nf + 4 * (nv + 1)
@@ -142,7 +99,7 @@ def measure(args):
         entry = {"nv": nv, "nf": nf, "border_vertices": int(border.sum().item()),
                  "bytes_must_move_per_step": step_bytes, "bytes_must_move_ring": ring_bytes}
         for k in launches:
-            entry[k] = stats(ms[k])
+            entry[k] = mb.stats(ms[k])
         entry["smooth"]["GB_per_s"] = round(
             (STEPS * step_bytes + ring_bytes) / (entry["smooth"]["ms_median"] * 1e-3) / 1e9, 1)
         entry["smooth"]["ratio_to_normals_alone"] = round(
@@ -159,36 +116,20 @@ def measure(args):
         res["meshes"][name] = entry
     if args.trace:
         return
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    mb.write_record(res, args.out)
 
 
 def merge_trace(args):
     """The kernels' own times out of a rocprofv3 kernel trace of `--trace`, into the JSON."""
     res = json.loads(open(args.out).read())
     turns = res["warmup"] + res["repeats"]
-    rows = {k: [] for k in KERNELS}
-    with open(args.merge_trace) as f:
-        for row in csv.DictReader(f):
-            for k in KERNELS:
-                if k in row["Kernel_Name"]:
-                    rows[k].append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
-    for k, per_turn in KERNELS.items():
-        rows[k].sort()
-        # (the turns are the last dispatches of the run: whatever built the meshes came before)
-        expected = per_turn * turns * len(MESHES)
-        if len(rows[k]) < expected:
-            raise SystemExit("%s: %d dispatches in the trace, expected %d"
-                             % (k, len(rows[k]), expected))
-        rows[k] = rows[k][-expected:]
+    rows = mb.keep_last(mb.trace_rows(args.merge_trace, KERNELS),
+                        {k: per_turn * turns * len(MESHES) for k, per_turn in KERNELS.items()})
     for at, name in enumerate(MESHES):
         own = {}
         for k, per_turn in KERNELS.items():
             mine = rows[k][(at * turns + res["warmup"]) * per_turn:(at + 1) * turns * per_turn]
-            own[k] = stats([(e - s) * 1e-6 for s, e in mine])
+            own[k] = mb.stats([(e - s) * 1e-6 for s, e in mine])
         entry = res["meshes"][name]
         step, ring = own["k_smooth_step"]["ms_median"], own["k_smooth_ring"]["ms_median"]
         own["k_smooth_step"]["GB_per_s"] = round(
@@ -198,42 +139,8 @@ def merge_trace(args):
         own["step_to_normals"] = round(step / own["k_vertex_area_normals"]["ms_median"], 3)
         own["ring_to_step"] = round(ring / step, 3)
         entry["kernel_trace"] = own
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def merge_box(args):
-    """bench.py's JSON line of the same visit, under "box"."""
-    res = json.loads(open(args.out).read())
-    lines = [l for l in open(args.merge_box).read().splitlines() if l.strip().startswith("{")]
-    res["box"] = json.loads(lines[-1])
-    line = json.dumps(res)
-    print(line)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--trace", action="store_true",
-                    help="only the launches (for a kernel trace); writes nothing")
-    ap.add_argument("--merge_trace", default=None,
-                    help="a rocprofv3 kernel_trace.csv of --trace: add the kernels' times (no GPU)")
-    ap.add_argument("--merge_box", default=None,
-                    help="a file with bench.py's JSON line of the same visit (no GPU)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "smooth_bench.json"))
-    args = ap.parse_args()
-    if args.merge_trace:
-        merge_trace(args)
-    elif args.merge_box:
-        merge_box(args)
-    else:
-        measure(args)
+    mb.write_record(res, args.out)
 
 
 if __name__ == "__main__":
-    main()
+    mb.main("smooth_bench", measure, merge_trace)
