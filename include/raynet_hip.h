@@ -1235,6 +1235,59 @@ int rn_mesh_fill_holes(rn_ctx *ctx, int64_t nv, const float *vertices, int64_t n
                        float *new_vertices, int32_t *new_faces, int32_t *source, int64_t *counts,
                        void *workspace, void *stream);
 
+/* ---- an indexed triangle mesh seen from cameras ----
+ *
+ * rn_mesh_render: for every pixel of V views of H x W pixels the face its ray hits first, the
+ * depth of the hit, where in the face it lies, and the vertices' colours and normals there.  All
+ * views go in one launch, one lane per pixel.
+ *
+ * All arrays are device memory; the inputs are never written.
+ *   nodes, leaves          the BVH of rn_mesh_build over the triangles vertices[faces[f]] (common.
+ *                          mesh_io.get_triangles), so that a leaf's triangle index is a face index
+ *   vertices [nv][3] f32, faces [nf][3] i32
+ *   colors   [nv][C] f32 or NULL, 1 <= C <= 4;  normals [nv][3] f32 or NULL
+ *   cameras  [V][15] f32   per view P_pinv [4][3] | centre [3]: what rn_mesh_depthmap takes
+ * Every output is written for all V H W pixels, always:
+ *   face   [V][H][W]    i32   the face hit, -1 on a miss
+ *   depth  [V][H][W]    f32   0 on a miss
+ *   bary   [V][H][W][2] f32   (u, v); (0, 0) on a miss
+ *   color  [V][H][W][C] f32   iff colors is given (NULL otherwise); 0 on a miss
+ *   normal [V][H][W][3] f32   iff normals is given (NULL otherwise); 0 on a miss
+ *
+ * The pixel of column x and row y: its ray, its first hit and its depth are rn_mesh_depthmap's --
+ * the destination project(P_pinv, (x, y, 1)) formed in float64 from the fp32 P_pinv and rounded
+ * once, the first hit of rn_mesh_raycast (the smallest fp32 key, the lower face on equal keys),
+ * the float64 distance of the hit to the centre rounded once: depth[view] has the bits
+ * rn_mesh_depthmap writes for that view.
+ *
+ * (u, v) are the fp32 Moeller-Trumbore coordinates of the winning face f, the ones its
+ * intersection test computed: with ray the ray's fp32 unit direction, o the centre, p0, p1, p2 the
+ * vertices of f, e1 = p1 - p0, e2 = p2 - p0, pvec = ray x e2, inv = 1 / (e1 . pvec), t = o - p0,
+ * q = t x e1: u = (t . pvec) inv, v = (ray . q) inv, every dot product ((a + b) + c), every
+ * operation fp32 and rounded on its own.  The hit is (1 - u - v) p0 + u p1 + v p2.
+ *
+ * Interpolation, in fp64, every operation rounded on its own (the library is built with
+ * -ffp-contract=off; tests/render_truth.py restates it in NumPy to the bit): U = (double) u,
+ * Vb = (double) v, Wb = (1.0 - U) - Vb; per component a = (Wb a0 + U a1) + Vb a2 of the three
+ * vertices' values widened to double.  A colour is (float) a.  A normal: l2 = (nx nx + ny ny) +
+ * nz nz; (float)(n_k / sqrt(l2)) if l2 > 0 and finite, else (0, 0, 0).
+ *
+ * A hit face that is not in [0, nf) or names a vertex outside [0, nv) keeps its face and depth and
+ * gets bary, color and normal 0.  Whatever faces holds, nothing is read or written out of bounds.
+ * The result does not depend on how pixels are dealt to lanes (a wavefront covers an 8 x 8 tile).
+ *
+ * RN_OK without a launch, nothing written: V == 0, or H W == 0, with valid sizes (whatever the
+ * pointers).  RN_ERR_INVALID, rn_last_error naming the entry, no launch, outputs untouched: a
+ * negative nv, nf, V, H or W; V > 4096; V H W > 2^31 - 1, or with colors V H W C > 2^31 - 1; C
+ * outside 1..4 when colors is given; nv > 2^31 - 2 or 3 nf > 2^31 - 1; nf < 1; with pixels to
+ * render a NULL nodes, leaves, vertices, faces, cameras, face, depth or bary, color NULL while
+ * colors is not or the reverse, the same for normal and normals. */
+int rn_mesh_render(rn_ctx *ctx, const float *nodes, const float *leaves, int64_t nv,
+                   const float *vertices, int64_t nf, const int32_t *faces, const float *colors,
+                   int32_t C, const float *normals, int32_t V, const float *cameras, int32_t H,
+                   int32_t W, int32_t *face, float *depth, float *bary, float *color, float *normal,
+                   void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

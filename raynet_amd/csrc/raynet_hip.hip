@@ -1258,5 +1258,9 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // corner table and the scan
 #include "raynet_holes.inl"
 
+// a surface mesh seen from cameras: face, depth, barycentrics, colours and normals per pixel over
+// raynet_mesh.inl's BVH
+#include "raynet_render.inl"
+
 // the surface of a belief grid: marching tetrahedra and the scan
 #include "raynet_isosurface.inl"

@@ -880,6 +880,47 @@ class HipContext(object):
                                               _ptr(nodes), _ptr(leaves), _ptr(depth_map),
                                               _stream()))
 
+    # ---- a mesh seen from cameras (raynet_amd/render.py) ---------------------------------------
+    def mesh_render(self, nodes, leaves, vertices, faces, cameras, H, W, colors=None, normals=None):
+        """rn_mesh_render: the BVH (nodes, leaves) of the triangles vertices[faces], vertices
+        (nv, 3) f32, faces (nf, 3) i32, cameras (V, 15) f32 rows P_pinv | centre, optional colors
+        (nv, C) f32 with C in 1..4 and normals (nv, 3) f32 -> (face (V, H, W) i32, depth (V, H, W)
+        f32, bary (V, H, W, 2) f32, color (V, H, W, C) f32 or None, normal (V, H, W, 3) f32 or
+        None): per pixel the face hit first (-1: none), the distance of the hit to the centre, its
+        Moeller-Trumbore (u, v) and the attributes interpolated there; 0 on a miss."""
+        nv, nf = _chk_mesh(vertices, faces)
+        H, W = int(H), int(W)
+        if cameras.dim() != 2 or cameras.shape[1] != 15:
+            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
+        V = int(cameras.shape[0])
+        _chk(cameras, torch.float32, 15 * V, "cameras")
+        _chk(nodes, torch.float32, 16 * max(nf - 1, 1), "nodes", align=16)
+        _chk(leaves, torch.float32, 12 * nf, "leaves", align=16)
+        C = 0
+        if colors is not None:
+            if colors.dim() != 2 or colors.shape[0] != nv or not 1 <= colors.shape[1] <= 4:
+                raise ValueError("colors: expected (%d, C) with C in 1..4, got %s"
+                                 % (nv, tuple(colors.shape)))
+            C = int(colors.shape[1])
+            _chk(colors, torch.float32, nv * C, "colors")
+        if normals is not None:
+            if tuple(normals.shape) != (nv, 3):
+                raise ValueError("normals: expected (%d, 3), got %s" % (nv, tuple(normals.shape)))
+            _chk(normals, torch.float32, 3 * nv, "normals")
+        device = vertices.device
+        face = torch.empty((V, H, W), dtype=torch.int32, device=device)
+        depth = torch.empty((V, H, W), dtype=torch.float32, device=device)
+        bary = torch.empty((V, H, W, 2), dtype=torch.float32, device=device)
+        color = None if colors is None else torch.empty((V, H, W, C), dtype=torch.float32,
+                                                        device=device)
+        normal = None if normals is None else torch.empty((V, H, W, 3), dtype=torch.float32,
+                                                          device=device)
+        self._check(self.lib.rn_mesh_render(
+            self._h, _ptr(nodes), _ptr(leaves), nv, _ptr(vertices), nf, _ptr(faces), _ptr(colors),
+            C, _ptr(normals), V, _ptr(cameras), H, W, _ptr(face), _ptr(depth), _ptr(bary),
+            _ptr(color), _ptr(normal), _stream()))
+        return face, depth, bary, color, normal
+
     def prof_begin(self, capacity=4096, only=None):
         """only: kernel family names to bracket (None = all of them)."""
         mask = 0xFFFFFFFF

@@ -337,3 +337,25 @@ class SurfaceCompleteness(Metric):
         predicted_pointcloud.index()
         distances, indexes = predicted_pointcloud.nearest_neighbors(ground_truth_pc.points)
         return np.minimum(distances, self.truncate), ground_truth_pc.points
+
+
+def photometric_error(rendered, image, mask):
+    """The image-space score of a rendered surface against a photograph:
+    rendered and image (H, W) or (H, W, C) arrays of one shape in [0, 1], mask (H, W) the pixels
+    the surface covers -> dict(coverage, mae, mse, psnr), in NumPy float64.  coverage: the share
+    of pixels covered; mae and mse: the mean absolute and the mean squared difference over the
+    covered pixels and all channels; psnr = 10 log10(1 / mse), inf at mse == 0.  Nothing covered:
+    coverage 0, the other three nan."""
+    a, b = np.asarray(rendered, np.float64), np.asarray(image, np.float64)
+    covered = np.asarray(mask, bool)
+    if a.shape != b.shape or a.ndim not in (2, 3) or covered.shape != a.shape[:2]:
+        raise ValueError("rendered %s, image %s and mask %s: (H, W[, C]) twice and (H, W)"
+                         % (a.shape, b.shape, covered.shape))
+    n = int(covered.sum())
+    coverage = n / float(covered.size) if covered.size else 0.0
+    if n == 0:
+        return dict(coverage=coverage, mae=float("nan"), mse=float("nan"), psnr=float("nan"))
+    diff = a[covered] - b[covered]
+    mse = float((diff * diff).mean())
+    psnr = float("inf") if mse == 0.0 else float(10.0 * np.log10(1.0 / mse))
+    return dict(coverage=coverage, mae=float(np.abs(diff).mean()), mse=mse, psnr=psnr)

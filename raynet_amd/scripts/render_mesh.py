@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Render a surface mesh from the cameras of a scene, and score it against their photographs.
+
+    python -m raynet_amd.scripts.render_mesh DATASET_DIR MESH.ply OUT_DIR \\
+        --dataset_type restrepo --start_end 0,12 [--planes color,depth] [--compare]
+
+MESH.ply is what `fuse_depth_maps` and `render_volume --mesh` write (volume.SurfaceMesh.save_ply).
+For every frame of --start_end / --skip_every the mesh is seen from the frame's camera at the
+scene's image size, all frames in one launch (volume.SurfaceMesh.render_scene, DESIGN.md section
+26), and OUT_DIR gets, of the --planes asked for (a comma-separated list),
+
+    color    render_%03d.png    the vertices' colours interpolated over the faces
+    normals  normals_%03d.png   the interpolated unit normals as (n + 1) / 2
+    shaded   shaded_%03d.png    a grey headlight image max(0, n . direction to the camera)
+    depth    depth_%03d.npy     (H, W) float32, 0 where the ray hits nothing: the wire format
+                                compute_metrics reads
+    faces    faces_%03d.npy     (H, W) int32 the face hit first, -1 where none, and with it
+             bary_%03d.npy      (H, W, 2) float32 where in that face
+
+The default is `color` for a mesh with colours and `shaded` for one without; `color` needs colours
+in the file, `normals` and `shaded` compute the normals of a mesh that has none.  --background
+R,G,B (0..255) is the colour of the pixels whose rays hit nothing.
+
+--compare scores each `color` render against the frame's image over the pixels the mesh covers
+(metrics.photometric_error): one line `view I: coverage C, mae M, psnr P` per frame, and
+OUT_DIR/render_metrics.json.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+PLANES = ("color", "normals", "shaded", "depth", "faces")
+
+
+def _ints(x):
+    return tuple(map(int, x.split(",")))
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Render a surface mesh from a scene's cameras")
+    p.add_argument("dataset_directory", help="Directory containing the input data")
+    p.add_argument("mesh_file", help="The surface mesh (PLY)")
+    p.add_argument("output_directory", help="Directory to save the rendered images")
+    p.add_argument("--planes", default=None,
+                   help="Comma-separated: %s (default: color if the mesh has colours, else shaded)"
+                   % ", ".join(PLANES))
+    p.add_argument("--background", default="0,0,0",
+                   help="R,G,B (0..255) of the pixels whose rays hit nothing")
+    p.add_argument("--compare", action="store_true",
+                   help="Score the color renders against the frames' images")
+    # the dataset and indexing flags of raynet_amd.scripts.forward_pass
+    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
+    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
+    p.add_argument("--start_end", type=_ints, default="0,5")
+    p.add_argument("--skip_every", type=int, default=0)
+    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
+                   default="filesystem")
+    p.add_argument("--illumination_condition", default="max")
+    return p
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if isinstance(args.start_end, str):
+        args.start_end = _ints(args.start_end)
+    if len(args.start_end) != 2:
+        parser.error("--start_end takes two numbers, START,END")
+    planes = None
+    if args.planes is not None:
+        planes = [x.strip() for x in args.planes.split(",") if x.strip()]
+        unknown = [x for x in planes if x not in PLANES]
+        if unknown or not planes:
+            parser.error("--planes takes a comma-separated list of %s, got %r"
+                         % (", ".join(PLANES), args.planes))
+    try:
+        background = _ints(args.background)
+    except ValueError:
+        background = ()
+    if len(background) != 3 or min(background) < 0 or max(background) > 255:
+        parser.error("--background takes three numbers R,G,B in 0..255, got %r" % args.background)
+    if args.compare and planes is not None and "color" not in planes:
+        parser.error("--compare scores the color renders: add color to --planes")
+    if not os.path.isfile(args.mesh_file):
+        parser.error("%s: no such file (fuse_depth_maps and render_volume --mesh write one)"
+                     % args.mesh_file)
+    from raynet_amd.common.scene import get_scene
+    from raynet_amd.metrics import photometric_error
+    from raynet_amd.volume import SurfaceMesh
+
+    mesh = SurfaceMesh.load_ply(args.mesh_file)
+    if planes is None:
+        planes = ["color" if mesh.colors is not None else "shaded"]
+    if "color" in planes and mesh.colors is None:
+        parser.error("--planes color: %s has no colours (fuse_depth_maps --color and render_volume "
+                     "--mesh --color write them)" % args.mesh_file)
+    if args.compare and "color" not in planes:
+        parser.error("--compare scores the color renders: %s has no colours" % args.mesh_file)
+    if mesh.empty:
+        parser.error("%s: the mesh is empty, there is no surface to render" % args.mesh_file)
+    if args.dataset_type == "dtu":
+        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
+                          illumination=args.illumination_condition,
+                          select_neighbors_based_on=args.select_neighbors_based_on)
+    else:
+        scene = get_scene("restrepo", args.dataset_directory,
+                          select_neighbors_based_on=args.select_neighbors_based_on)
+    start, end = args.start_end
+    frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
+    if not frames:
+        parser.error("--start_end selects no frame of the scene")
+    if ("normals" in planes or "shaded" in planes) and mesh.normals is None:
+        mesh.compute_normals()
+    os.makedirs(args.output_directory, exist_ok=True)
+    from PIL import Image as PILImage
+    cameras = [scene.get_image(i).camera for i in frames]
+    rendered = mesh.render_scene(scene, frames)
+
+    def path(pattern, i):
+        return os.path.join(args.output_directory, pattern % (i,))
+
+    scores = []
+    for k, i in enumerate(frames):
+        if "color" in planes:
+            PILImage.fromarray(rendered.rgb8(k, background)).save(path("render_%03d.png", i))
+        if "normals" in planes:
+            PILImage.fromarray(rendered.normal_rgb8(k)).save(path("normals_%03d.png", i))
+        if "shaded" in planes:
+            PILImage.fromarray(rendered.shaded8(k, cameras)).save(path("shaded_%03d.png", i))
+        if "depth" in planes:
+            np.save(path("depth_%03d.npy", i), rendered.depth[k].cpu().numpy())
+        if "faces" in planes:
+            np.save(path("faces_%03d.npy", i), rendered.face[k].cpu().numpy())
+            np.save(path("bary_%03d.npy", i), rendered.bary[k].cpu().numpy())
+        if args.compare:
+            image = np.asarray(scene.get_image(i).image, np.float32)
+            color = rendered.color[k].cpu().numpy()
+            if image.shape[2] != color.shape[2]:            # a grey photograph
+                image = np.repeat(image[:, :, :1], color.shape[2], axis=2)
+            score = photometric_error(color, image, rendered.mask[k].cpu().numpy())
+            print("view %d: coverage %.4f, mae %.4f, psnr %.2f"
+                  % (i, score["coverage"], score["mae"], score["psnr"]))
+            scores.append(dict(view=i, **score))
+    if args.compare:
+        with open(os.path.join(args.output_directory, "render_metrics.json"), "w") as f:
+            json.dump(dict(mesh=os.path.basename(args.mesh_file), faces=int(len(mesh.faces)),
+                           views=scores), f, indent=1)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

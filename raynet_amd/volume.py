@@ -275,6 +275,19 @@ class SurfaceMesh(object):
         from .mesh import MeshRaycaster
         return MeshRaycaster(self.triangles())
 
+    # ---- images of the surface (render.py) ----------------------------
+    def render(self, cameras, H, W, raycaster=None):
+        """-> render.MeshRender: per pixel of every camera the face hit first, its depth, where in
+        the face, and this mesh's colours and normals (where it has them) interpolated there."""
+        from .render import render_mesh
+        return render_mesh(self, cameras, H, W, raycaster)
+
+    def render_scene(self, scene, frame_idxs, raycaster=None):
+        """`render` from the cameras of the scene's frames `frame_idxs`, at the scene's image
+        size."""
+        H, W = scene.image_shape
+        return self.render([scene.get_image(int(i)).camera for i in frame_idxs], H, W, raycaster)
+
     def pointcloud(self, n_samples, seed=0):
         """-> raynet_amd.pointcloud.Pointcloud of `n_samples` area-weighted points of the
         surface (MeshRaycaster.sample_surface), for the point-cloud filters and the metrics."""
