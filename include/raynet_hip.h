@@ -1288,6 +1288,82 @@ int rn_mesh_render(rn_ctx *ctx, const float *nodes, const float *leaves, int64_t
                    int32_t W, int32_t *face, float *depth, float *bary, float *color, float *normal,
                    void *stream);
 
+/* ---- the photographs baked into a texture atlas of a surface mesh ----
+ *
+ * The atlas (csrc/raynet_texture_args.h, namespace rn_tex; pure integer arithmetic): T is the
+ * number of texel steps along a chart's leg, 1 <= T <= 1024.  A cell is S = T + 5 texels square
+ * and holds two faces; cells = (nf + 1) / 2, cells_per_row = Cw >= 1 is the caller's, rows =
+ * ceil(cells / Cw), Wt = Cw S, Ht = rows S.  Texel centres are at whole coordinates.  The owner of
+ * texel (tx, ty): cx = tx / S, i = tx % S, cy = ty / S, j = ty % S, k = cy Cw + cx, lower =
+ * (i + j <= T + 3), f = 2 k + (lower ? 0 : 1); a texel with f >= nf is empty.  The corners of a
+ * chart in cell-local texels (a, b): lower p0 (1, 1), p1 (T + 1, 1), p2 (1, T + 1); upper
+ * p0 (T + 3, T + 3), p1 (3, T + 3), p2 (T + 3, 3).  The point with barycentrics (u, v) for
+ * (p1, p2) lies at a = 1 + u T, b = 1 + v T (lower) or a = (T + 3) - u T, b = (T + 3) - v T
+ * (upper), so that the 2 x 2 footprint of a bilinear lookup anywhere in a face's chart touches
+ * only texels that face owns; the texels a face owns outside its triangle are its gutter.
+ *
+ * rn_texture_bake: one lane per texel.  All arrays are device memory; the inputs are never
+ * written.  vertices [nv][3] f32, faces [nf][3] i32, normals [nv][3] f32 or NULL; cameras, H, W,
+ * C, images, depths, tol, min_cos, border and mode are exactly rn_project_colors's.  texture
+ * [Ht][Wt][C] f32, weight [Ht][Wt] f32 and views [Ht][Wt] u32 are written for all Ht Wt texels,
+ * always, also with V == 0.
+ *
+ * Per texel with owner f and cell-local (i, j), in fp64, every operation rounded on its own and
+ * in the order written (the library is built with -ffp-contract=off; tests/texture_truth.py
+ * restates it in NumPy to the bit):
+ *   lower:  u0 = (double)(i - 1) / (double)T,        v0 = (double)(j - 1) / (double)T
+ *   upper:  u0 = (double)((T + 3) - i) / (double)T,  v0 = (double)((T + 3) - j) / (double)T
+ *   u = u0 > 0 ? u0 : 0;  v likewise;  s = u + v;  if s > 1: u = u / s, v = v / s
+ *     (a gutter texel takes the colour of a point on its face's rim)
+ *   Wb = (1.0 - u) - v;  p_k = (Wb p0_k + u p1_k) + v p2_k of the three vertices widened to
+ *     double (rn_mesh_render's interpolation); p is NOT rounded to fp32
+ *   the normal: with normals, n_k = (Wb n0_k + u n1_k) + v n2_k; with NULL the face's e1 x e2 of
+ *     e1 = p1 - p0, e2 = p2 - p0 in fp64, (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x)
+ *     as rn_vertex_area_normals forms it.  It is not normalised (the facing test carries nn); a
+ *     zero normal means no facing test and w = 1.
+ *   then, for the views in ascending order, rn_project_colors's projection, in-view, facing and
+ *     occlusion tests, its bilinear fetch and its blend (mode 0) or best view (mode 1), on that
+ *     fp64 point and normal: a NaN fails every test, a view that does not count reads pixel
+ *     (0, 0), texture = (float) of the result or 0 where no view counted, weight = (float) den,
+ *     views bit v is set iff view v counted.
+ * An empty texel gets colour 0, weight 0, views 0, and so does a texel whose face names a vertex
+ * outside [0, nv).  Whatever faces holds, nothing is read or written out of bounds.  The result
+ * does not depend on how texels are dealt to lanes (a wavefront covers an 8 x 8 tile of texels).
+ *
+ * RN_OK without a launch, nothing written: nf == 0 with valid scalars (whatever the pointers).
+ * RN_ERR_INVALID, rn_last_error naming the entry, no launch, outputs untouched: a negative nv or
+ * nf, nv > 2^31 - 2 or 3 nf > 2^31 - 1; T outside 1..1024; cells_per_row outside 1..16384; with
+ * faces Wt or Ht > 16384, or Wt Ht C > 2^31 - 1; everything rn_project_colors refuses of V, H, W,
+ * C, tol, min_cos, border and mode; with faces a NULL vertices, faces, texture, weight or views,
+ * and a NULL cameras or images with V > 0. */
+int rn_texture_bake(rn_ctx *ctx, int64_t nv, const float *vertices, int64_t nf, const int32_t *faces,
+                    const float *normals, int32_t T, int32_t cells_per_row, int32_t V,
+                    const double *cameras, int32_t H, int32_t W, int32_t C, const float *images,
+                    const float *depths, double tol, double min_cos, double border, int32_t mode,
+                    float *texture, float *weight, uint32_t *views, void *stream);
+
+/* rn_texture_sample: the lookup behind a render, one lane per pixel of rn_mesh_render's face [n]
+ * i32 and bary [n][2] f32 planes, flattened; texture [Ht][Wt][C] f32 of the atlas of nf faces, T
+ * and cells_per_row; color [n][C] f32 is written for all n pixels.
+ *   U = (double) u, Vb = (double) v; lower = (f even), k = f / 2, cx = k % Cw, cy = k / Cw;
+ *   a = 1.0 + U (double)T (lower) or (double)(T + 3) - U (double)T (upper), b likewise from Vb;
+ *   x = (double)(cx S) + a, y = (double)(cy S) + b
+ *   bilinear != 0: x0 = floor(x), x1 = min(x0 + 1, Wt - 1), fx = x - x0, likewise y;
+ *     top = t00 + fx (t01 - t00), bot = t10 + fx (t11 - t10), color = (float)(top + fy (bot - top))
+ *     of the four texels widened to double
+ *   bilinear == 0: the texel at (rint(x), rint(y)), half to even.
+ * Colour 0 for a face outside [0, nf) (-1 is one) and for U or Vb outside [0, 1] (a NaN is).
+ * Every load lies inside the atlas whatever the inputs hold.
+ *
+ * RN_OK without a launch, nothing written: n == 0 with valid scalars.  RN_ERR_INVALID,
+ * rn_last_error naming the entry, no launch, color untouched: a negative n or nf, 3 nf > 2^31 - 1;
+ * T or cells_per_row out of range; C outside 1..4; bilinear neither 0 nor 1; n C > 2^31 - 1; with
+ * faces Wt or Ht > 16384 or Wt Ht C > 2^31 - 1; with pixels a NULL face, bary or color, and a NULL
+ * texture with nf > 0. */
+int rn_texture_sample(rn_ctx *ctx, int64_t n, const int32_t *face, const float *bary, int64_t nf,
+                      int32_t T, int32_t cells_per_row, int32_t C, const float *texture,
+                      int32_t bilinear, float *color, void *stream);
+
 /* hipEvent pair on `stream`; rn_timer_stop returns elapsed milliseconds after
  * synchronising on the stop event (bench.py's per-kernel timing). */
 int rn_timer_start(rn_ctx *ctx, void *stream);

@@ -57,6 +57,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_mesh_args.h"),
             os.path.join(CSRC, "raynet_render.inl"), os.path.join(CSRC, "raynet_render_args.h"),
             os.path.join(CSRC, "raynet_scan.inl"), os.path.join(CSRC, "raynet_scan_args.h"),
+            os.path.join(CSRC, "raynet_texture.inl"), os.path.join(CSRC, "raynet_texture_args.h"),
             HEADER]
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
@@ -234,6 +235,9 @@ SIGNATURES = {
     "rn_mesh_fill_holes": [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "rn_mesh_render": [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P,
                        _P],
+    "rn_texture_bake": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _D, _D, _D, _I,
+                        _P, _P, _P, _P],
+    "rn_texture_sample": [_P, _L, _P, _P, _L, _I, _I, _I, _P, _I, _P, _P],
     "rn_prof_offsets": [_P, _P],
     "rn_selftest_arith": [_P, _I, _P, _P, _P],
     "rn_selftest_quotient": [_P, _I, _P, _P, _P, _P],

@@ -1262,5 +1262,10 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // raynet_mesh.inl's BVH
 #include "raynet_render.inl"
 
+// the photographs baked into a texture atlas of a surface mesh, and the lookup behind a render
+// 
+#include "raynet_texture.inl"
+
 // the surface of a belief grid: marching tetrahedra and the scan
 #include "raynet_isosurface.inl"
+

@@ -921,6 +921,58 @@ class HipContext(object):
             _ptr(color), _ptr(normal), _stream()))
         return face, depth, bary, color, normal
 
+    # ---- a texture atlas from the photographs (raynet_amd/texture.py) --------------------------
+    def texture_bake(self, vertices, faces, normals, T, cells_per_row, cameras, images, depths, tol,
+                     min_cos, border, mode, texture, weight, views):
+        """rn_texture_bake: vertices (nv, 3) f32, faces (nf, 3) i32, normals (nv, 3) f32 or None,
+        cameras (V, 15) f64, images (V, H, W, C) f32, depths (V, H, W) f32 or None -> texture
+        (>= Ht, Wt, C) f32, weight (>= Ht, Wt) f32, views (>= Ht, Wt) int32 (the bits of the u32
+        mask) of the atlas of T steps per leg and cells_per_row cells per row; mode 0: blend, 1:
+        best."""
+        nv, nf = _chk_mesh(vertices, faces)
+        T, Cw, V = int(T), int(cells_per_row), len(cameras)
+        if images.dim() != 4 or images.shape[0] != V:
+            raise ValueError("images: expected (%d, H, W, C), got %s" % (V, tuple(images.shape)))
+        H, W, C = (int(s) for s in images.shape[1:])
+        if cameras.dim() != 2 or cameras.shape[1] != 15:
+            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
+        texels = 0
+        if 1 <= T <= 1024 and 1 <= Cw <= 16384:         # (else the entry refuses)
+            texels = Cw * (T + 5) * (((nf + 1) // 2 + Cw - 1) // Cw) * (T + 5)
+        _chk(normals, torch.float32, 3 * nv, "normals", optional=True)
+        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
+        _chk(images, torch.float32, V * H * W * C, "images")
+        _chk(depths, torch.float32, V * H * W, "depths", optional=True)
+        _chk(texture, torch.float32, texels * C, "texture")
+        _chk(weight, torch.float32, texels, "weight")
+        _chk(views, torch.int32, texels, "views")
+        self._check(self.lib.rn_texture_bake(
+            self._h, nv, _ptr(vertices), nf, _ptr(faces), _ptr(normals), T, Cw, V, _ptr(cameras),
+            H, W, C, _ptr(images), _ptr(depths), float(tol), float(min_cos), float(border),
+            int(mode), _ptr(texture), _ptr(weight), _ptr(views), _stream()))
+
+    def texture_sample(self, face, bary, n_faces, T, cells_per_row, texture, bilinear, color):
+        """rn_texture_sample: face [n] i32 and bary (n, 2) f32 (rn_mesh_render's planes,
+        flattened), texture (Ht, Wt, C) f32 of the atlas of n_faces faces -> color (>= n, C) f32:
+        the atlas at every pixel's place in its face's chart, bilinear or the nearest texel; 0
+        where the pixel sees no face."""
+        n = int(face.numel())
+        if texture.dim() != 3 or not 1 <= texture.shape[2] <= 4:
+            raise ValueError("texture: expected (Ht, Wt, C) with C in 1..4, got %s"
+                             % (tuple(texture.shape),))
+        C = int(texture.shape[2])
+        nf, T, Cw = int(n_faces), int(T), int(cells_per_row)
+        texels = 0
+        if 1 <= T <= 1024 and 1 <= Cw <= 16384 and nf >= 0:
+            texels = Cw * (T + 5) * (((nf + 1) // 2 + Cw - 1) // Cw) * (T + 5)
+        _chk(face, torch.int32, n, "face")
+        _chk(bary, torch.float32, 2 * n, "bary")
+        _chk(texture, torch.float32, texels * C, "texture")
+        _chk(color, torch.float32, n * C, "color")
+        self._check(self.lib.rn_texture_sample(self._h, n, _ptr(face), _ptr(bary), nf, T, Cw, C,
+                                               _ptr(texture), 1 if bilinear else 0, _ptr(color),
+                                               _stream()))
+
     def prof_begin(self, capacity=4096, only=None):
         """only: kernel family names to bracket (None = all of them)."""
         mask = 0xFFFFFFFF

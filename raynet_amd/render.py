@@ -75,6 +75,14 @@ class MeshRender(object):
         grey = (self.normal[view] * to_camera).sum(-1).clamp(0, 1) * self.mask[view]
         return _rgb8(grey.cpu().numpy()[:, :, None])
 
+    def textured(self, texture, bilinear=True):
+        """-> a MeshRender with the same planes whose colour is `texture` (texture.MeshTexture of
+        the rendered mesh's faces) looked up at every pixel's face and barycentrics, bilinear or
+        the nearest texel (texture.sample_texture)."""
+        from .texture import sample_texture
+        return MeshRender(self.face, self.depth, self.bary,
+                          sample_texture(self, texture, bilinear), self.normal)
+
 
 def render_mesh(mesh, cameras, H, W, raycaster=None):
     """-> MeshRender of `mesh` (volume.SurfaceMesh; its uint8 colours go in as /255 float32) seen

@@ -40,7 +40,7 @@ import sys
 
 import numpy as np
 
-from . import mesh_flags
+from . import mesh_flags, texture_flags
 from .convert_to_pointcloud import find_format
 
 
@@ -78,6 +78,7 @@ def build_parser():
                    help="--mesh_cloud: how many area-weighted points to draw")
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
     mesh_flags.add_arguments(p)
+    texture_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.render_volume
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -114,6 +115,7 @@ def main(argv=None):
     if args.gt and args.confidence_weights:
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
     mesh_flags.check(parser, args)
+    texture_flags.check(parser, args)
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
 
@@ -131,6 +133,7 @@ def main(argv=None):
     if args.color and len(frames) > 32:
         parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
                      "--skip_every" % len(frames))
+    texture_flags.check_frames(parser, args, frames)
     weights = None
     if args.gt:
         depth_maps = [scene.get_depth_map(i) for i in frames]
@@ -155,7 +158,7 @@ def main(argv=None):
     if args.volume:
         volume.save(args.volume)
     mesh = mesh_flags.apply(volume.mesh(args.min_weight), args, volume)
-    if (args.normals or args.color or args.mesh_cloud) and mesh.empty:
+    if (args.normals or args.color or args.mesh_cloud or args.texture is not None) and mesh.empty:
         parser.error("the fused surface is empty: no voxel pair straddles a measured depth")
     if args.normals or args.color:
         mesh.compute_normals()
@@ -163,6 +166,10 @@ def main(argv=None):
         mesh.colorize(scene, frames,
                       tol=float(np.sqrt((mesh_flags.voxel_sides(volume) ** 2).sum())))
     mesh.save_ply(args.output_mesh)
+    if args.texture is not None:
+        texture_flags.write(parser, args, mesh, scene, frames,
+                            float(np.sqrt((mesh_flags.voxel_sides(volume) ** 2).sum())),
+                            args.output_mesh)
     if args.mesh_cloud:
         mesh.pointcloud(args.mesh_samples, args.seed).save_ply(args.mesh_cloud)
     return 0

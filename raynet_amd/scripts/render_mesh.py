@@ -24,6 +24,14 @@ R,G,B (0..255) is the colour of the pixels whose rays hit nothing.
 --compare scores each `color` render against the frame's image over the pixels the mesh covers
 (metrics.photometric_error): one line `view I: coverage C, mae M, psnr P` per frame, and
 OUT_DIR/render_metrics.json.
+
+--texture T bakes the selected frames' images (at most 32) into a texture atlas of T texel steps
+per chart leg (volume.SurfaceMesh.textured) and writes texture_%03d.png per
+frame -- the same render with the atlas looked up at every pixel's face and barycentrics,
+bilinear, or the nearest texel with --texture_nearest -- and atlas.png.  --texture_mode and
+--texture_normals are the bake's; --texture_tolerance is the slack of its occlusion test in scene
+units (default: the median edge length of the mesh).  With --compare every frame gets a second
+line `view I texture: coverage C, mae M, psnr P`, and render_metrics.json a list `texture_views`.
 """
 import argparse
 import json
@@ -31,6 +39,8 @@ import os
 import sys
 
 import numpy as np
+
+from . import texture_flags
 
 PLANES = ("color", "normals", "shaded", "depth", "faces")
 
@@ -51,6 +61,10 @@ def build_parser():
                    help="R,G,B (0..255) of the pixels whose rays hit nothing")
     p.add_argument("--compare", action="store_true",
                    help="Score the color renders against the frames' images")
+    texture_flags.add_arguments(p, nearest=True)
+    p.add_argument("--texture_tolerance", type=float, default=None,
+                   help="--texture: the slack of the occlusion test in scene units (default: the "
+                        "median edge length of the mesh)")
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -62,6 +76,12 @@ def build_parser():
     return p
 
 
+def _median_edge(mesh):
+    tri = np.asarray(mesh.vertices, np.float64)[np.asarray(mesh.faces, np.int64)]
+    edges = np.concatenate([tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 1], tri[:, 0] - tri[:, 2]])
+    return float(np.median(np.sqrt((edges ** 2).sum(1))))
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -69,6 +89,11 @@ def main(argv=None):
         args.start_end = _ints(args.start_end)
     if len(args.start_end) != 2:
         parser.error("--start_end takes two numbers, START,END")
+    texture_flags.check(parser, args)
+    if args.texture_tolerance is not None and args.texture is None:
+        parser.error("--texture_tolerance goes with --texture T")
+    if args.texture_tolerance is not None and not 0.0 <= args.texture_tolerance < float("inf"):
+        parser.error("--texture_tolerance takes a finite distance, 0 or more")
     planes = None
     if args.planes is not None:
         planes = [x.strip() for x in args.planes.split(",") if x.strip()]
@@ -112,6 +137,7 @@ def main(argv=None):
     frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
     if not frames:
         parser.error("--start_end selects no frame of the scene")
+    texture_flags.check_frames(parser, args, frames)
     if ("normals" in planes or "shaded" in planes) and mesh.normals is None:
         mesh.compute_normals()
     os.makedirs(args.output_directory, exist_ok=True)
@@ -122,7 +148,13 @@ def main(argv=None):
     def path(pattern, i):
         return os.path.join(args.output_directory, pattern % (i,))
 
-    scores = []
+    textured = None
+    if args.texture is not None:
+        tol = _median_edge(mesh) if args.texture_tolerance is None else args.texture_tolerance
+        baked = texture_flags.bake(parser, args, mesh, scene, frames, tol)
+        textured = rendered.textured(baked.with_unseen(), bilinear=not args.texture_nearest)
+        baked.save_png(os.path.join(args.output_directory, "atlas.png"))
+    scores, texture_scores = [], []
     for k, i in enumerate(frames):
         if "color" in planes:
             PILImage.fromarray(rendered.rgb8(k, background)).save(path("render_%03d.png", i))
@@ -144,10 +176,21 @@ def main(argv=None):
             print("view %d: coverage %.4f, mae %.4f, psnr %.2f"
                   % (i, score["coverage"], score["mae"], score["psnr"]))
             scores.append(dict(view=i, **score))
+        if textured is not None:
+            PILImage.fromarray(textured.rgb8(k, background)).save(path("texture_%03d.png", i))
+        if textured is not None and args.compare:
+            color = textured.color[k].cpu().numpy()
+            if image.shape[2] != color.shape[2]:
+                image = np.repeat(image[:, :, :1], color.shape[2], axis=2)
+            score = photometric_error(color, image, rendered.mask[k].cpu().numpy())
+            print("view %d texture: coverage %.4f, mae %.4f, psnr %.2f"
+                  % (i, score["coverage"], score["mae"], score["psnr"]))
+            texture_scores.append(dict(view=i, **score))
     if args.compare:
         with open(os.path.join(args.output_directory, "render_metrics.json"), "w") as f:
             json.dump(dict(mesh=os.path.basename(args.mesh_file), faces=int(len(mesh.faces)),
-                           views=scores), f, indent=1)
+                           views=scores, **({} if textured is None else
+                                            dict(texture_views=texture_scores))), f, indent=1)
             f.write("\n")
     return 0
 

@@ -42,7 +42,7 @@ import sys
 
 import numpy as np
 
-from . import mesh_flags
+from . import mesh_flags, texture_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -79,6 +79,7 @@ def build_parser():
     p.add_argument("--depth_tolerance", type=float, default=1.0,
                    help="--color: the slack of the occlusion test, in voxel diagonals")
     mesh_flags.add_arguments(p)
+    texture_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.forward_pass
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -108,6 +109,7 @@ def main(argv=None):
     if not (args.depth_tolerance >= 0.0 and args.depth_tolerance < float("inf")):
         parser.error("--depth_tolerance takes a finite number of voxel diagonals, 0 or more")
     mesh_flags.check(parser, args, mesh_requested=bool(args.mesh))
+    texture_flags.check(parser, args, mesh_requested=bool(args.mesh))
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -128,6 +130,7 @@ def main(argv=None):
     if args.color and len(frames) > 32:
         parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
                      "--skip_every" % len(frames))
+    texture_flags.check_frames(parser, args, frames)
     for i, r in zip(frames, volume.render_scene(scene, frames)):
         np.save(os.path.join(args.output_directory, "depth_%03d.npy" % (i,)),
                 getattr(r, args.plane))
@@ -146,6 +149,9 @@ def main(argv=None):
                           mode=args.color_mode)
         if args.mesh:
             mesh.save_ply(args.mesh)
+        if args.mesh and args.texture is not None:
+            texture_flags.write(parser, args, mesh, scene, frames,
+                                args.depth_tolerance * float(np.sqrt((voxel ** 2).sum())), args.mesh)
         if args.mesh_cloud:
             if mesh.empty:
                 parser.error("no voxel reaches --threshold %g: the surface is empty and has no "

@@ -221,6 +221,51 @@ class SurfaceMesh(object):
         self.colors = to_rgb8(got.colors, got.seen, unseen)
         return got.views
 
+    # ---- a texture atlas (texture.py) ---------------------------------
+    def textured(self, scene, frame_idxs, T, tol, min_cos=0.0, mode="blend", normals="face"):
+        """-> texture.MeshTexture: the images of the scene's frames `frame_idxs` (at most 32) baked
+        into an atlas of T texel steps per chart leg.  The occluder is the mesh's own depth map
+        per frame plus `tol`, exactly as for `colorize`; normals "face" tests a texel against its
+        face's normal, "vertex" against the interpolated vertex normals (computed if absent)."""
+        from .appearance import scene_views
+        from .texture import bake_texture
+        if self.empty:
+            raise ValueError("the mesh is empty: there is no surface to texture")
+        cameras, images = scene_views(scene, frame_idxs)
+        H, W = np.asarray(images[0]).shape[:2]
+        caster = self.raycaster()
+        depth_maps = [caster.depth_map(cam, H, W) for cam in cameras]
+        return bake_texture(self, cameras, images, T, depth_maps, tol=tol, min_cos=min_cos,
+                            mode=mode, normals=normals)
+
+    def save_obj(self, path, texture, unseen=(0.5, 0.5, 0.5)):
+        """Writes STEM.obj (`v`, `vt`, `f a/ta b/tb c/tc`, 1-based, `mtllib` / `usemtl`), STEM.mtl
+        (`map_Kd STEM.png`) and STEM.png beside it, STEM being `path` without its extension: the
+        mesh with `texture` (texture.MeshTexture of this mesh's faces), texels no view saw in
+        `unseen`.  Every face has three texture vertices of its own, in face order.  -> the three
+        paths."""
+        import os
+        from .texture import face_uvs
+        if texture.layout.n_faces != len(self.faces):
+            raise ValueError("a texture of %d faces for a mesh of %d"
+                             % (texture.layout.n_faces, len(self.faces)))
+        stem = os.path.splitext(path)[0]
+        name = os.path.basename(stem)
+        obj, mtl, png = stem + ".obj", stem + ".mtl", stem + ".png"
+        uvs = face_uvs(len(self.faces), texture.layout).reshape(-1, 2)
+        with open(obj, "w") as f:
+            f.write("# raynet_amd surface mesh\nmtllib %s.mtl\nusemtl %s\n" % (name, name))
+            f.write("".join("v %.9g %.9g %.9g\n" % tuple(v) for v in self.vertices.tolist()))
+            f.write("".join("vt %.17g %.17g\n" % tuple(t) for t in uvs.tolist()))
+            f.write("".join("f %d/%d %d/%d %d/%d\n" % (a + 1, 3 * k + 1, b + 1, 3 * k + 2, c + 1,
+                                                       3 * k + 3)
+                            for k, (a, b, c) in enumerate(self.faces.tolist())))
+        with open(mtl, "w") as f:
+            f.write("newmtl %s\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n"
+                    % (name, name))
+        texture.save_png(png, unseen)
+        return obj, mtl, png
+
     # ---- file ------------------------------------------------------------------------------
     def save_ply(self, path):
         """A binary little-endian PLY: `vertex` x y z float -- then nx ny nz float where the mesh
