@@ -737,6 +737,31 @@ def test_box_scatter_equals_direct_sum(torch, oracle_mod, layout):
     scale = np.abs(truth).max()
     assert np.abs(outs[True][0] - truth).max() < 2e-6 * scale
     assert np.abs(outs[False][0] - truth).max() < 2e-5 * scale
+    # ... and the boxes do what the docstring says, by the kernel's own counters: a context of its
+    # own per pinned tile shape, two sweeps with the device idle in between -- scatter_state()
+    # then holds the first sweep's counters (tests/test_scatter_paths_gpu.py).  The census is the
+    # host's count of the same thing.  (128 x 32 tiles: one chunk of the patches' 57 -- tile 6,
+    # chunk 1, a box of 4158 voxels -- is above the 4096 of the LDS box; 256 x 16: none is.)
+    from scatter_truth import census
+    from raynet_amd.hip_implementations.context import HipContext
+    from raynet_amd.hip_implementations.options import PathOptions
+    Sr_d, packed_d, rvc_d = (torch.from_numpy(a).cuda() for a in (Sr, packed, rvc))
+    for level in (0, 1):
+        own = HipContext(M, D, 2, 4, H, W, 3, [-1, -1, -1, 1, 1, 1], grid)
+        own.set_voxel_grid(torch.from_numpy(vg).cuda())
+        own.set_options(PathOptions(box_level=level, box_pin=True))
+        for sweep in range(2):
+            part = torch.zeros((own.acc_size(),), device="cuda")
+            own.scene_bp_sweep(Sr_d, packed_d, rvc_d, acc_in, torch.zeros((n, M), device="cuda"),
+                               part, first_sweep=True, patch_rows=True)
+            torch.cuda.synchronize()
+        c = census(rvi, rvc, M, level)
+        lv, chunks, overflowed = own.scatter_state()
+        assert (lv, chunks, overflowed) == (level, c["chunks"], c["overflowed"])
+        if layout == "shuffled":
+            assert overflowed > 0 and c["nofit"] > 0
+        elif layout == "patches" and level == 1:
+            assert overflowed == 0
 
 
 def test_box_scatter_with_caller_made_voxel_lists(torch, oracle_mod):
