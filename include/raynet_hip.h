@@ -1167,6 +1167,89 @@ int rn_mesh_simplify(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t 
                      float *vertices_out, int32_t *faces_out, int32_t *source, int32_t *cluster,
                      int64_t *counts, void *workspace, void *stream);
 
+/* ---- quadric-error placement of the vertices of a clustered mesh ----
+ *
+ * rn_mesh_place_quadric: every output vertex of rn_mesh_simplify moves from the mean of its
+ * cluster to the point that minimises the weighted sum of its squared distances to the planes of
+ * the input faces that touch the cluster, plus a small pull towards the mean (Lindstrom's
+ * placement for vertex clustering).  It consumes what rn_mesh_simplify returns -- `cluster` and
+ * the mean positions -- and writes new positions for the same output vertices; faces, `source`
+ * and the order of everything are rn_mesh_simplify's and stay.
+ *
+ * cell [3] f64 is a HOST array, the sides of a cell; all other arrays are device memory.
+ * vertices_in [nv][3] f32, faces_in [nf][3] i32, cluster [nv] i32 (the output index of each input
+ * vertex, anything outside [0, nvo) for none) and positions_in [nvo][3] f32 are never written.
+ *   positions_out [nvo][3] f32   the placed vertices; every row is written
+ *   counts        [2]      i64   the vertices whose row of positions_out differs in its bits from
+ *                                positions_in; the vertices with two or more members that kept
+ *                                positions_in's bits because the placement was refused
+ * workspace: 8-byte aligned, at least rn_mesh_place_quadric_workspace_bytes(nv, nf, nvo) = 88 nvo
+ * bytes (-1 for sizes the entry refuses), laid out [nvo][11] i64: the ten sums S[0..9] and the
+ * member count n of every output vertex.  Nothing beyond that size is touched.
+ *
+ * Every floating-point operation is fp64 and rounded on its own, in the order written (the library
+ * is built with -ffp-contract=off); only + - * /, sqrt, rint (to nearest, ties to even),
+ * comparisons and conversions occur, so a NumPy restatement gives the same bits
+ * (tests/quadric_truth.py).  L = max(cell_x, cell_y, cell_z).
+ *
+ * 1. Every S and n is 0.
+ * 2. Every input vertex v with 0 <= cluster[v] < nvo adds 1 to n of that output vertex.
+ * 3. Every input face (i_0, i_1, i_2) with all three indices in [0, nv), a, b, c its corners as
+ *    doubles:
+ *        e1 = b - a;  e2 = c - a
+ *        N_x = e1_y e2_z - e1_z e2_y;  N_y = e1_z e2_x - e1_x e2_z;  N_z = e1_x e2_y - e1_y e2_x
+ *        s = (N_x N_x + N_y N_y) + N_z N_z;  len = sqrt(s)
+ *    adds nothing unless len is finite and > 0; otherwise
+ *        n = N / len;  share = (0.5 len) / (L L);  w = share if share < 1, else 1
+ *    and for each corner j = 0, 1, 2 with k = cluster[i_j]: nothing if k is outside [0, nvo) or
+ *    equals cluster[i_j'] of an earlier corner j' < j (a face adds once per distinct cluster, and
+ *    the faces the clustering drops add too); otherwise, with m = positions_in[k] and p the corner,
+ *        r = (p - m) / L   per axis;   nothing unless -2 <= r_i <= 2 on all three axes
+ *        d = -((n_x r_x + n_y r_y) + n_z r_z)
+ *    (a member and its mean share a cell, so the test on r only refuses a caller's garbage; the
+ *    bound below rests on it) and the ten terms
+ *        (w n_x) n_x, (w n_x) n_y, (w n_x) n_z, (w n_y) n_y, (w n_y) n_z, (w n_z) n_z,
+ *        (w n_x) d, (w n_y) d, (w n_z) d, w
+ *    each as the integer rint(term * 2^30), are added to S[0..9] of k by 64-bit integer atomics.
+ *    |n_i| <= 1, |r_i| <= 2 and w <= 1 give |d| <= 2 sqrt(3) and |term| < 3.47, so every integer
+ *    is below 2^32 in magnitude; one add per face and cluster and nf < 2^30 keep every sum below
+ *    2^62.
+ * 4. Every output vertex k: positions_in[k]'s BITS if n <= 1 or S[9] == 0.  Otherwise T_i =
+ *    (double) S[i] / 2^30 (the conversion to nearest, ties to even), ridge = regularization T_9,
+ *        M = [T_0 + ridge, T_1, T_2; T_1, T_3 + ridge, T_4; T_2, T_4, T_5 + ridge],  y = -(T_6, T_7, T_8)
+ *    and M x = y by L D L^T without pivoting:
+ *        d_0 = M_00;  l_10 = M_01 / d_0;  l_20 = M_02 / d_0
+ *        d_1 = M_11 - l_10 M_01;  e = M_12 - l_20 M_01;  l_21 = e / d_1
+ *        d_2 = (M_22 - l_20 M_02) - l_21 e
+ *        z_0 = y_0;  z_1 = y_1 - l_10 z_0;  z_2 = (y_2 - l_20 z_0) - l_21 z_1
+ *        g_i = z_i / d_i
+ *        x_2 = g_2;  x_1 = g_1 - l_21 x_2;  x_0 = (g_0 - l_10 x_1) - l_20 x_2
+ *    A pivot d_i that is not > 0, or an l or an x that is not finite, gives positions_in's bits.
+ *    Then x_i is clamped to +- (max_move cell_i) / L and
+ *        out_i = (float) ((double) m_i + L x_i);
+ *    an out_i that is not finite gives positions_in's bits for the whole vertex.
+ * The ridge makes M positive definite wherever a face added, so no pseudo-inverse and no
+ * singular-value threshold are needed: along a direction the planes do not constrain (a flat
+ * region, the line of a crease) the vertex stays at the mean.
+ *
+ * The result is one fixed set of arrays whatever the launch geometry or the order in which the
+ * hardware ran the threads.  Whatever faces_in, cluster and the positions hold, nothing is read or
+ * written out of bounds, and no loop has a trip count that depends on data.
+ *
+ * nvo == 0: RN_OK, counts = {0, 0}, no kernel launch.  RN_ERR_INVALID, rn_last_error naming the
+ * entry, no launch, outputs untouched: a NULL ctx, nv or nf negative, nv > 2^31 - 2, 3 nf > 2^31 -
+ * 1, nvo negative or > nv, a NULL cell, a cell_k not finite or <= 0, regularization outside
+ * [2^-20, 1] or NaN, max_move not > 0 (inf is taken), a NULL counts, and with nvo > 0 a NULL
+ * vertices_in / cluster / positions_in / positions_out / workspace, a NULL faces_in with nf > 0, a
+ * workspace that is not 8-byte aligned, positions_out equal to vertices_in, faces_in, cluster,
+ * positions_in or workspace. */
+int64_t rn_mesh_place_quadric_workspace_bytes(int64_t nv, int64_t nf, int64_t nvo);
+int rn_mesh_place_quadric(rn_ctx *ctx, int64_t nv, const float *vertices_in, int64_t nf,
+                          const int32_t *faces_in, const int32_t *cluster, int64_t nvo,
+                          const float *positions_in, const double cell[3], double regularization,
+                          double max_move, float *positions_out, int64_t *counts, void *workspace,
+                          void *stream);
+
 /* ---- the small holes of an indexed triangle mesh capped ----
  *
  * rn_mesh_fill_holes: every simple boundary loop of at most max_edges edges gets a vertex at the

@@ -53,6 +53,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
             os.path.join(CSRC, "raynet_simplify.inl"),
             os.path.join(CSRC, "raynet_simplify_args.h"),
+            os.path.join(CSRC, "raynet_quadric.inl"), os.path.join(CSRC, "raynet_quadric_args.h"),
             os.path.join(CSRC, "raynet_holes.inl"), os.path.join(CSRC, "raynet_holes_args.h"),
             os.path.join(CSRC, "raynet_mesh_args.h"),
             os.path.join(CSRC, "raynet_render.inl"), os.path.join(CSRC, "raynet_render_args.h"),
@@ -231,6 +232,8 @@ SIGNATURES = {
     "rn_mesh_smooth": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],
     "rn_mesh_simplify_workspace_bytes": [_L, _L, _P],
     "rn_mesh_simplify": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rn_mesh_place_quadric_workspace_bytes": [_L, _L, _L],
+    "rn_mesh_place_quadric": [_P, _L, _P, _L, _P, _P, _L, _P, _P, _D, _D, _P, _P, _P, _P],
     "rn_mesh_fill_holes_workspace_bytes": [_L, _L],
     "rn_mesh_fill_holes": [_P, _L, _P, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "rn_mesh_render": [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P,
@@ -276,6 +279,7 @@ def load():
     lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_simplify_workspace_bytes.restype = ctypes.c_int64
+    lib.rn_mesh_place_quadric_workspace_bytes.restype = ctypes.c_int64
     lib.rn_mesh_fill_holes_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib

@@ -1254,6 +1254,10 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // section 24)
 #include "raynet_simplify.inl"
 
+// quadric-error placement of the clustered vertices: the planes of the faces summed per cluster
+// in fixed point, a 3 x 3 solve per vertex
+#include "raynet_quadric.inl"
+
 // the small holes of a surface mesh capped: the union-find over the boundary half-edges, the
 // corner table and the scan
 #include "raynet_holes.inl"

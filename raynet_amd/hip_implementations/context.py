@@ -534,6 +534,51 @@ class HipContext(object):
         nv_out, nf_out = (int(x) for x in counts.tolist())
         return vertices_out[:nv_out], faces_out[:nf_out], source[:nv_out], cluster
 
+    # ---- quadric-error placement of the clustered vertices (raynet_amd/simplify.py) -------------
+    def mesh_place_quadric_workspace_bytes(self, nv, nf, nvo):
+        """rn_mesh_place_quadric_workspace_bytes: the bytes rn_mesh_place_quadric needs for nv
+        input vertices, nf input faces and nvo output vertices (88 per output vertex)."""
+        n = int(self.lib.rn_mesh_place_quadric_workspace_bytes(int(nv), int(nf), int(nvo)))
+        if n < 0:
+            raise ValueError("rn_mesh_place_quadric_workspace_bytes: bad sizes (nv %d, nf %d, "
+                             "nvo %d)" % (nv, nf, nvo))
+        return n
+
+    def mesh_place_quadric(self, vertices, faces, cluster, positions, cell, regularization=2.0 ** -10,
+                           max_move=1.0, workspace=None, out=None):
+        """rn_mesh_place_quadric: the input mesh of mesh_simplify (vertices (nv, 3) f32, faces
+        (nf, 3) i32), its `cluster` [nv] i32 and its output vertices `positions` (nvo, 3) f32, the
+        sides of a cell (cell [3] > 0 on the host) -> (positions_out (nvo, 3) f32, counts [2]
+        int64 on the host): every output vertex at the minimiser of its summed squared distances to
+        the planes of the faces around its cluster, `regularization` in [2^-20, 1] pulling it to
+        `positions`, no coordinate farther than `max_move` cell sides from there; counts: the
+        vertices whose bits changed, the vertices of two or more members that kept theirs because
+        the placement was refused.  workspace: a uint8 tensor of at least
+        mesh_place_quadric_workspace_bytes(nv, nf, nvo) bytes, 8-byte aligned (allocated if None).
+        One read-back: the counts."""
+        nv, nf = _chk_mesh(vertices, faces)
+        _chk(cluster, torch.int32, nv, "cluster")
+        if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
+            raise ValueError("positions: expected a (nvo, 3) tensor, got %s" % (
+                tuple(positions.shape) if isinstance(positions, torch.Tensor)
+                else type(positions).__name__,))
+        nvo = len(positions)
+        _chk(positions, torch.float32, 3 * nvo, "positions")
+        if nvo > nv:
+            raise ValueError("positions: at most the %d rows of vertices, got %d" % (nv, nvo))
+        c = (ctypes.c_double * 3)(*_three_floats(cell, "cell"))
+        need = self.mesh_place_quadric_workspace_bytes(nv, nf, nvo)
+        workspace = _workspace(workspace, need, vertices.device)
+        if out is None:
+            out = torch.empty((nvo, 3), dtype=torch.float32, device=vertices.device)
+        _chk(out, torch.float32, 3 * nvo, "out")
+        counts = torch.empty((2,), dtype=torch.int64, device=vertices.device)
+        self._check(self.lib.rn_mesh_place_quadric(
+            self._h, nv, _ptr(vertices), nf, _ptr(faces), _ptr(cluster), nvo, _ptr(positions), c,
+            float(regularization), float(max_move), _ptr(out), _ptr(counts), _ptr(workspace),
+            _stream()))
+        return out, counts.cpu().numpy()
+
     # ---- small holes of a mesh capped (raynet_amd/holes.py) ------------------------------------
     def mesh_fill_holes_workspace_bytes(self, nv, nf):
         """rn_mesh_fill_holes_workspace_bytes: the bytes rn_mesh_fill_holes needs for nv vertices

@@ -24,6 +24,13 @@
                              the faces that name the same three vertices the first one stays)
     (raynet_amd.simplify).  Prints
     `simplify: cell X voxel sides, V -> V' vertices, F -> F' faces`.
+--simplify_placement P       where the one vertex of a cell goes: `mean` (the default) or `quadric`,
+                             the point nearest to the planes of the faces around the cell, which
+                             keeps ridges, corners and eaves sharp where the mean rounds them off
+--simplify_regularization X  --simplify_placement quadric: the pull back to the mean, as a share of
+                             the faces' summed weights, in [2^-20, 1] (default 2^-10)
+    (DESIGN.md section 28).  With `quadric` a second line:
+    `placement: quadric, K of V' vertices moved, F fell back, farthest move M cell sides`.
 
 --smooth N                   Taubin smoothing, N iterations (a step with lambda, then one with mu)
 --smooth_lambda L            the factor of the first step, in (0, 1] (default 0.5)
@@ -44,6 +51,9 @@ SIMPLIFY_FLAGS = ("simplify", "simplify_keep_duplicates")
 SMOOTH_FLAGS = ("smooth", "smooth_lambda", "smooth_mu", "smooth_max_move", "smooth_free_boundary")
 FLAGS = COMPONENT_FLAGS + SIMPLIFY_FLAGS + SMOOTH_FLAGS
 HOLE_FLAGS = ("fill_holes",)        # registered behind FLAGS; its stage runs after the components'
+PLACEMENT_FLAGS = ("simplify_placement", "simplify_regularization")     # behind those; --simplify's
+PLACEMENTS = ("mean", "quadric")
+MIN_REGULARIZATION = 2.0 ** -20
 MAX_ITERATIONS = 10000
 MIN_HOLE_EDGES, MAX_HOLE_EDGES = 3, 65536
 
@@ -72,10 +82,16 @@ def add_arguments(p):
                    help="--smooth: do not pin the vertices on the border of the mesh")
     p.add_argument("--fill_holes", type=int, default=None,
                    help="Cap the boundary loops of the mesh that have at most this many edges")
+    p.add_argument("--simplify_placement", choices=PLACEMENTS, default=None,
+                   help="--simplify: the vertex of a cell at the mean of its members (mean) or "
+                        "nearest to the planes of the faces around it (quadric)")
+    p.add_argument("--simplify_regularization", type=float, default=None,
+                   help="--simplify_placement quadric: the pull back to the mean, in [2^-20, 1] "
+                        "(2^-10)")
 
 
 def given(args, flags=FLAGS):
-    return [f for f in flags if getattr(args, f) is not None]
+    return [f for f in flags if getattr(args, f, None) is not None]
 
 
 def check(parser, args, mesh_requested=True):
@@ -107,6 +123,15 @@ def check(parser, args, mesh_requested=True):
     if args.simplify is None and given(args, SIMPLIFY_FLAGS):
         parser.error("--%s goes with --simplify X" % given(args, SIMPLIFY_FLAGS)[0])
     needs_mesh(SIMPLIFY_FLAGS, "simplification is")
+
+    x = getattr(args, "simplify_regularization", None)
+    if x is not None and not MIN_REGULARIZATION <= x <= 1.0:
+        parser.error("--simplify_regularization takes a share in [2^-20, 1]")
+    if x is not None and getattr(args, "simplify_placement", None) != "quadric":
+        parser.error("--simplify_regularization goes with --simplify_placement quadric")
+    if args.simplify is None and given(args, PLACEMENT_FLAGS):
+        parser.error("--%s goes with --simplify X" % given(args, PLACEMENT_FLAGS)[0])
+    needs_mesh(PLACEMENT_FLAGS, "placement is")
 
     if args.smooth is not None and not 1 <= args.smooth <= MAX_ITERATIONS:
         parser.error("--smooth takes a number of iterations, 1..%d" % MAX_ITERATIONS)
@@ -172,10 +197,23 @@ def simplify(mesh, args, voxel, origin):
                         axis=0)
         steps = np.where(np.isfinite(low), np.floor((low - anchor) / cell), 0.0)
         anchor = anchor + np.minimum(steps, 0.0) * cell
-    out = mesh.simplified(cell, origin=anchor,
-                          drop_duplicate_faces=not args.simplify_keep_duplicates)
+    if getattr(args, "simplify_placement", None) != "quadric":
+        out = mesh.simplified(cell, origin=anchor,
+                              drop_duplicate_faces=not args.simplify_keep_duplicates)
+        stats = None
+    else:
+        x = getattr(args, "simplify_regularization", None)
+        out, stats = mesh.simplified(cell, origin=anchor,
+                                     drop_duplicate_faces=not args.simplify_keep_duplicates,
+                                     placement="quadric",
+                                     regularization=2.0 ** -10 if x is None else x,
+                                     return_stats=True)
     print("simplify: cell %g voxel sides, %d -> %d vertices, %d -> %d faces"
           % (args.simplify, len(mesh.vertices), len(out.vertices), len(mesh.faces), len(out.faces)))
+    if stats is not None:
+        print("placement: quadric, %d of %d vertices moved, %d fell back, farthest move %.3f cell "
+              "sides" % (stats["moved"], len(out.vertices), stats["fell_back"],
+                         stats["farthest_move"]))
     return out
 
 

@@ -151,25 +151,32 @@ class SurfaceMesh(object):
         return (out, stats) if return_stats else out
 
     # ---- simplification (simplify.py) ---------------------------------
-    def simplified(self, cell, origin=None, drop_duplicate_faces=True):
+    def simplified(self, cell, origin=None, drop_duplicate_faces=True, placement="mean",
+                   regularization=2.0 ** -10, max_move=1.0, return_stats=False):
         """-> a new SurfaceMesh with the vertices of every cell of a uniform grid (sides `cell`, a
         number or one per axis; simplify.simplify_mesh: the keywords are its own) merged at their
-        mean, without the faces and vertices that vanish that way.  Colours are those of each
+        mean, without the faces and vertices that vanish that way; with placement="quadric" the
+        merged vertices lie where the planes of the faces around them meet (creases stay sharp)
+        instead, `regularization` and `max_move` as in simplify_mesh.  Colours are those of each
         cluster's smallest vertex, normals are recomputed if and only if this mesh has them.  An
-        empty mesh gives an empty mesh, without the GPU."""
+        empty mesh gives an empty mesh, without the GPU.  return_stats: (the mesh, simplify_mesh's
+        dict of the placement)."""
         from . import simplify
         if self.empty:
+            simplify.check_placement(placement, regularization, max_move)
             simplify.cluster_grid(self.vertices, cell, origin)
-            return SurfaceMesh(self.vertices.copy(), self.faces.copy(), self.normals, self.colors)
-        vertices, faces, source = simplify.simplify_mesh(self.vertices, self.faces, cell, origin,
-                                                         drop_duplicate_faces)
+            out = SurfaceMesh(self.vertices.copy(), self.faces.copy(), self.normals, self.colors)
+            return (out, {"moved": 0, "fell_back": 0, "farthest_move": 0.0}) if return_stats else out
+        vertices, faces, source, stats = simplify.simplify_mesh(
+            self.vertices, self.faces, cell, origin, drop_duplicate_faces, placement,
+            regularization, max_move, True)
         out = SurfaceMesh(vertices, faces, None,
                           None if self.colors is None else self.colors[source])
         if self.normals is not None and out.empty:      # (everything in one cell)
             out.normals = np.zeros_like(out.vertices)
         elif self.normals is not None:
             out.compute_normals()
-        return out
+        return (out, stats) if return_stats else out
 
     # ---- smoothing (smoothing.py, DESIGN.md section 23) -------------------------------------
     def smoothed(self, iterations=10, lam=0.5, mu=-0.53, fixed="boundary", max_move=None):
