@@ -55,7 +55,7 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
             os.path.join(CSRC, "raynet_simplify_args.h"),
             os.path.join(CSRC, "raynet_quadric.inl"), os.path.join(CSRC, "raynet_quadric_args.h"),
             os.path.join(CSRC, "raynet_holes.inl"), os.path.join(CSRC, "raynet_holes_args.h"),
-            os.path.join(CSRC, "raynet_mesh_args.h"),
+            os.path.join(CSRC, "raynet_mesh_args.h"), os.path.join(CSRC, "raynet_views_args.h"),
             os.path.join(CSRC, "raynet_render.inl"), os.path.join(CSRC, "raynet_render_args.h"),
             os.path.join(CSRC, "raynet_scan.inl"), os.path.join(CSRC, "raynet_scan_args.h"),
             os.path.join(CSRC, "raynet_texture.inl"), os.path.join(CSRC, "raynet_texture_args.h"),

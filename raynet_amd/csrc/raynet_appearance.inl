@@ -79,6 +79,10 @@ __global__ __launch_bounds__(BLOCK) void k_project_colors(ColorArgs a) {
         ny = a.normals[rn_app::xyz_index(i, 1)];
         nz = a.normals[rn_app::xyz_index(i, 2)];
     }
+    // rn_view::observe<C> (raynet_views_args.h), written out: through the call this kernel's code
+    // changes and two of seven timed figures were slower than this text's by more than the
+    // noise (profiles/view_step_bench.json).  The bake of an atlas calls it, and a GPU test
+    // holds the two to the same bits at the corners of the charts.
     const double nn = (nx * nx + ny * ny) + nz * nz;
     const bool facing = nn > 0.0;                       // (no normals: nn == 0)
     const double mc2 = a.min_cos * a.min_cos;

@@ -2,8 +2,8 @@
 // rn_vertex_area_normals / rn_project_colors (raynet_appearance.inl), host-only and free of HIP so
 // that they compile into a stand-alone program (tests/appearance_args_main.cpp, built with the
 // address and undefined-behaviour sanitizers by tests/test_appearance_cpu.py).  The launchers act
-// on the verdicts; the kernels guard and address their reads with the constexpr functions below
-// and with the mesh guards of raynet_mesh_args.h.
+// on the verdicts; the kernels guard and address their reads with the mesh guards of
+// raynet_mesh_args.h, and k_project_colors's per-view step is raynet_views_args.h's observe.
 #pragma once
 
 #include <cmath>
@@ -11,16 +11,17 @@
 #include <cstdint>
 
 #include "raynet_mesh_args.h"
+#include "raynet_views_args.h"
 
 namespace rn_app {
 
 using rn_mesh::Verdict, rn_mesh::INVALID, rn_mesh::EMPTY, rn_mesh::LAUNCH;
 using rn_mesh::INT32_LIMIT, rn_mesh::sizes_ok;
 using rn_mesh::vertex_in, rn_mesh::corner_in, rn_mesh::clamp_slot, rn_mesh::xyz_index;
+using rn_view::CAMERA_DOUBLES, rn_view::image_index, rn_view::pixel_in;
 
 constexpr int MAX_VIEWS = 32;           // one bit of the `views` word each
 constexpr int MAX_CHANNELS = 4;
-constexpr int CAMERA_DOUBLES = 15;      // P [3][4] row-major | centre [3]
 
 // rn_vertex_area_normals.  The scalars first, then nv == 0 (nothing to write: EMPTY, whatever the
 // pointers), then the pointers: faces and corners are read only where there are faces.
@@ -57,15 +58,10 @@ inline Verdict colors_args(bool have_ctx, int64_t n, const void *points, int32_t
 }
 
 // ---- what the kernels guard and address with (constexpr: the same functions on the device):
-// rn_mesh's for the mesh, and for the images ----
-// pixel (view, y, x) of a [V][H][W] map, channel c of a [V][H][W][C] image
+// rn_mesh's for the mesh, rn_view's for the images.  depth_index: pixel (view, y, x) of a
+// [V][H][W] map ----
 constexpr size_t depth_index(int v, int y, int x, int H, int W) {
-    return ((size_t)v * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
+    return rn_view::map_index(v, y, x, H, W);
 }
-constexpr size_t image_index(int v, int y, int x, int c, int H, int W, int C) {
-    return depth_index(v, y, x, H, W) * (size_t)C + (size_t)c;
-}
-// a pixel coordinate of a view that counts lies in [0, extent - 1]; everything else reads pixel 0
-constexpr bool pixel_in(int at, int extent) { return at >= 0 && at < extent; }
 
 }  // namespace rn_app

@@ -38,18 +38,12 @@ __global__ __launch_bounds__(BLOCK) void k_tsdf_integrate(FusionArgs a) {
     const double x_max = (double)(a.W - 1) - a.border, y_max = (double)(a.H - 1) - a.border;
     double num = 0.0, den = 0.0;
     for (int v = 0; v < a.V; v++) {
-        const double *__restrict__ cam = a.cameras + rn_fusion::CAMERA_DOUBLES * v;    // uniform
-        const double h0 = ((cam[0] * x + cam[1] * y) + cam[2] * z) + cam[3];
-        const double h1 = ((cam[4] * x + cam[5] * y) + cam[6] * z) + cam[7];
-        const double h2 = ((cam[8] * x + cam[9] * y) + cam[10] * z) + cam[11];
-        const double X = h0 / h2, Y = h1 / h2;
-        const double dx = cam[12] - x, dy = cam[13] - y, dz = cam[14] - z;
-        const double dd = (dx * dx + dy * dy) + dz * dz;
-        // every test is a comparison that a NaN fails
-        bool ok = h2 > 0.0 && h2 < INFINITY && dd > 0.0 && X >= a.border && X <= x_max &&
-                  Y >= a.border && Y <= y_max;
+        const rn_view::Projection p = rn_view::project(
+            a.cameras + rn_fusion::CAMERA_DOUBLES * v, x, y, z, a.border, x_max, y_max);  // uniform
+        const double dd = p.dd;
+        bool ok = p.ok;
         // a view that does not count reads pixel (0, 0): every load is inside the arrays
-        const int xr = (int)rint(ok ? X : 0.0), yr = (int)rint(ok ? Y : 0.0);   // half to even
+        const int xr = (int)rint(ok ? p.X : 0.0), yr = (int)rint(ok ? p.Y : 0.0);   // half to even
         const size_t pixel = rn_fusion::map_index(v, rn_fusion::pixel_in(yr, a.H) ? yr : 0,
                                                   rn_fusion::pixel_in(xr, a.W) ? xr : 0, a.H, a.W);
         const double zm = a.depths[pixel];

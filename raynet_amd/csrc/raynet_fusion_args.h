@@ -14,10 +14,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "raynet_views_args.h"
+
 namespace rn_fusion {
 
+// the camera rows, and pixel (view, y, x) of a [V][H][W] map: a pixel coordinate of a view that
+// counts lies in [0, extent - 1]; everything else reads pixel 0
+using rn_view::CAMERA_DOUBLES, rn_view::map_index, rn_view::pixel_in;
+
 constexpr int MAX_VIEWS = 4096;         // rejects garbage; not a capacity
-constexpr int CAMERA_DOUBLES = 15;      // P [3][4] row-major | centre [3]
 
 enum Verdict { INVALID = -1, LAUNCH = 1 };
 
@@ -42,6 +47,7 @@ inline Verdict integrate_args(bool have_ctx, int32_t V, const void *cameras, int
 constexpr int64_t voxels(int32_t gx, int32_t gy, int32_t gz) {
     return (int64_t)gx * (int64_t)gy * (int64_t)gz;
 }
+// (one thread per voxel and no grid-stride loop: every voxel needs its block, however many)
 constexpr int64_t blocks(int64_t G, int block) { return (G + block - 1) / block; }
 constexpr bool voxel_in(int64_t g, int64_t G) { return g >= 0 && g < G; }
 
@@ -60,12 +66,6 @@ constexpr int axis_x(const Voxel &v) { return v.i; }
 constexpr int axis_y(const Voxel &v, int32_t gx) { return gx + v.j; }
 constexpr int axis_z(const Voxel &v, int32_t gx, int32_t gy) { return gx + gy + v.k; }
 
-// pixel (view, y, x) of a [V][H][W] map
-constexpr size_t map_index(int v, int y, int x, int H, int W) {
-    return ((size_t)v * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
-}
-// a pixel coordinate of a view that counts lies in [0, extent - 1]; everything else reads pixel 0
-constexpr bool pixel_in(int at, int extent) { return at >= 0 && at < extent; }
 // floats of a [V][H][W] map
 constexpr size_t map_extent(int V, int H, int W) {
     return V > 0 ? map_index(V - 1, H - 1, W - 1, H, W) + 1 : 0;

@@ -7,10 +7,11 @@
 //                             the chart are integer arithmetic (raynet_texture_args.h); its point
 //                             on the face and the normal there are formed in fp64 and stay fp64;
 //                             then, for the views in ascending order, rn_project_colors's
-//                             per-view step, restated here: projection, the in-view, facing and
-//                             occlusion tests, a bilinear fetch of C channels, the blend or the
-//                             best view.  The camera rows are the same for every lane (scalar
-//                             loads); nothing is shared between lanes.
+//                             per-view step, called (rn_view::observe of raynet_views_args.h):
+//                             projection, the in-view, facing and occlusion tests, a bilinear
+//                             fetch of C channels, the blend or the best view.  The camera rows
+//                             are the same for every lane (scalar loads); nothing is shared
+//                             between lanes.
 //   k_texture_sample<C>       one lane per pixel of rn_mesh_render's face / bary planes: the chart
 //                             position of (u, v), a bilinear or nearest fetch from the atlas.
 //
@@ -116,78 +117,14 @@ __global__ __launch_bounds__(BLOCK) void k_texture_bake(BakeArgs a) {
         ny = e1z * e2x - e1x * e2z;
         nz = e1x * e2y - e1y * e2x;
     }
-    // ---- rn_project_colors's per-view step, on the fp64 point and normal ----
-    const double nn = (nx * nx + ny * ny) + nz * nz;
-    const bool facing = nn > 0.0;
-    const double mc2 = a.min_cos * a.min_cos;
-    const double x_max = (double)(a.W - 1) - a.border, y_max = (double)(a.H - 1) - a.border;
-    double num[C], best[C], den = 0.0, best_w = -1.0;
+    // rn_project_colors's per-view step, on the fp64 point and normal
+    const rn_view::Views views{a.V, a.cameras, a.H, a.W, a.images, a.depths, a.tol, a.min_cos,
+                               a.border, a.mode};
+    const rn_view::Observation<C> seen = rn_view::observe<C>(views, x, y, z, nx, ny, nz);
 #pragma unroll
-    for (int c = 0; c < C; c++) num[c] = best[c] = 0.0;
-    uint32_t seen = 0;
-    for (int vw = 0; vw < a.V; vw++) {
-        const double *__restrict__ cam = a.cameras + rn_app::CAMERA_DOUBLES * vw;   // uniform
-        const double h0 = ((cam[0] * x + cam[1] * y) + cam[2] * z) + cam[3];
-        const double h1 = ((cam[4] * x + cam[5] * y) + cam[6] * z) + cam[7];
-        const double h2 = ((cam[8] * x + cam[9] * y) + cam[10] * z) + cam[11];
-        const double X = h0 / h2, Y = h1 / h2;
-        const double dx = cam[12] - x, dy = cam[13] - y, dz = cam[14] - z;
-        const double dd = (dx * dx + dy * dy) + dz * dz;
-        // every test is a comparison that a NaN fails
-        bool ok = h2 > 0.0 && h2 < INFINITY && dd > 0.0 && X >= a.border && X <= x_max &&
-                  Y >= a.border && Y <= y_max;
-        double w = 1.0;
-        if (facing) {
-            const double dot = (nx * dx + ny * dy) + nz * dz, q = nn * dd;
-            const double dot2 = dot * dot;
-            ok = ok && dot > 0.0 && dot2 > mc2 * q;
-            w = dot2 / q;
-        }
-        // a view that does not count reads pixel (0, 0): every load is inside the arrays
-        const double Xs = ok ? X : 0.0, Ys = ok ? Y : 0.0;
-        if (a.depths) {
-            const int xr = (int)rint(Xs), yr = (int)rint(Ys);           // half to even
-            const float zf = a.depths[rn_app::depth_index(vw, rn_app::pixel_in(yr, a.H) ? yr : 0,
-                                                          rn_app::pixel_in(xr, a.W) ? xr : 0,
-                                                          a.H, a.W)];
-            const double lim = (double)zf + a.tol;
-            ok = ok && zf > 0.0f && dd <= lim * lim;
-        }
-        const double xf = floor(Xs), yf = floor(Ys);
-        const double fx = Xs - xf, fy = Ys - yf;
-        int x0 = (int)xf, y0 = (int)yf;
-        x0 = rn_app::pixel_in(x0, a.W) ? x0 : 0;
-        y0 = rn_app::pixel_in(y0, a.H) ? y0 : 0;
-        const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-        double col[C];
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const double i00 = a.images[rn_app::image_index(vw, y0, x0, c, a.H, a.W, C)],
-                         i01 = a.images[rn_app::image_index(vw, y0, x1, c, a.H, a.W, C)],
-                         i10 = a.images[rn_app::image_index(vw, y1, x0, c, a.H, a.W, C)],
-                         i11 = a.images[rn_app::image_index(vw, y1, x1, c, a.H, a.W, C)];
-            const double top = i00 + fx * (i01 - i00), bot = i10 + fx * (i11 - i10);
-            col[c] = top + fy * (bot - top);
-        }
-        if (ok) {
-            seen |= 1u << vw;
-            den = den + w;
-            const bool better = w > best_w;         // strictly: the first of equal weights stays
-            best_w = better ? w : best_w;
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                num[c] = num[c] + w * col[c];
-                best[c] = better ? col[c] : best[c];
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const double blend = num[c] / den;
-        a.texture[at * C + c] = seen ? (float)(a.mode == 0 ? blend : best[c]) : 0.0f;
-    }
-    a.weight[at] = (float)den;
-    a.views[at] = seen;
+    for (int c = 0; c < C; c++) a.texture[at * C + c] = seen.color[c];
+    a.weight[at] = seen.weight;
+    a.views[at] = seen.views;
 }
 
 struct SampleArgs {
@@ -232,8 +169,7 @@ __global__ __launch_bounds__(BLOCK) void k_texture_sample(SampleArgs a) {
                              t01 = a.texture[rn_tex::texel_index(x1, y0, a.Wt) * C + c],
                              t10 = a.texture[rn_tex::texel_index(x0, y1, a.Wt) * C + c],
                              t11 = a.texture[rn_tex::texel_index(x1, y1, a.Wt) * C + c];
-                const double top = t00 + fx * (t01 - t00), bot = t10 + fx * (t11 - t10);
-                out[c] = (float)(top + fy * (bot - top));
+                out[c] = (float)rn_view::bilerp(t00, t01, t10, t11, fx, fy);
             }
         } else {
             const int64_t xr = (int64_t)rint(x), yr = (int64_t)rint(y);     // half to even

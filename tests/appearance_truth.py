@@ -75,11 +75,34 @@ def pack_cameras(cameras):
     return rows
 
 
-def project_colors(points, normals, cameras, images, depths, tol, min_cos, border, mode):
-    """points [n, 3] f32, normals [n, 3] f32 or None, cameras [V, 15] f64, images [V, H, W, C]
+def bilerp(i00, i01, i10, i11, fx, fy):
+    """The four neighbours i<row><column> at the fractions (fx, fy): along x first, then y."""
+    top = i00 + fx * (i01 - i00)
+    bot = i10 + fx * (i11 - i10)
+    return top + fy * (bot - top)
+
+
+def project_points(cam, x, y, z, border, x_max, y_max):
+    """One camera row and float64 points -> (X, Y, dx, dy, dz, dd, ok): the pixel, the vector to
+    the centre, its squared length, and whether the point lies in front of the camera, off its
+    centre and inside the image less the border.  (Under np.errstate(all="ignore").)"""
+    h = [((cam[4 * k] * x + cam[4 * k + 1] * y) + cam[4 * k + 2] * z) + cam[4 * k + 3]
+         for k in range(3)]
+    X, Y = h[0] / h[2], h[1] / h[2]
+    dx, dy, dz = cam[12] - x, cam[13] - y, cam[14] - z
+    dd = (dx * dx + dy * dy) + dz * dz
+    ok = (h[2] > 0) & (h[2] < np.inf) & (dd > 0) & (X >= border) & (X <= x_max) & \
+        (Y >= border) & (Y <= y_max)
+    return X, Y, dx, dy, dz, dd, ok
+
+
+def observe(points, normals, cameras, images, depths, tol, min_cos, border, mode):
+    """The per-view step of the definition, stated once: points [n, 3] f64, normals [n, 3] f64 or
+    None (as a zero normal: no facing test, weight 1), cameras [V, 15] f64, images [V, H, W, C]
     f32, depths [V, H, W] f32 or None, mode 0 / 1 -> (colors [n, C] f32, weight [n] f32,
     views [n] uint32)."""
-    p = np.asarray(points, F).reshape(-1, 3).astype(D)
+    p = np.asarray(points, D).reshape(-1, 3)
+    nr = np.zeros_like(p) if normals is None else np.asarray(normals, D).reshape(-1, 3)
     n = len(p)
     cameras = np.asarray(cameras, D).reshape(-1, 15)
     images = np.asarray(images, F)
@@ -88,37 +111,21 @@ def project_colors(points, normals, cameras, images, depths, tol, min_cos, borde
     tol, min_cos, border = D(tol), D(min_cos), D(border)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     with np.errstate(all="ignore"):
-        if normals is not None:
-            nr = np.asarray(normals, F).reshape(-1, 3).astype(D)
-            nx, ny, nz = nr[:, 0], nr[:, 1], nr[:, 2]
-            nn = (nx * nx + ny * ny) + nz * nz
-            facing = nn > 0
-        else:
-            facing = np.zeros(n, bool)
+        nx, ny, nz = nr[:, 0], nr[:, 1], nr[:, 2]
+        nn = (nx * nx + ny * ny) + nz * nz
+        facing = nn > 0
         mc2 = min_cos * min_cos
         x_max, y_max = D(W - 1) - border, D(H - 1) - border
-        num = np.zeros((n, C), D)
-        best = np.zeros((n, C), D)
-        den = np.zeros(n, D)
-        best_w = np.full(n, -1.0, D)
+        num, best = np.zeros((n, C), D), np.zeros((n, C), D)
+        den, best_w = np.zeros(n, D), np.full(n, -1.0, D)
         seen = np.zeros(n, np.uint32)
         for v in range(V):
-            cam = cameras[v]
-            h = [((cam[4 * k] * x + cam[4 * k + 1] * y) + cam[4 * k + 2] * z) + cam[4 * k + 3]
-                 for k in range(3)]
-            X, Y = h[0] / h[2], h[1] / h[2]
-            dx, dy, dz = cam[12] - x, cam[13] - y, cam[14] - z
-            dd = (dx * dx + dy * dy) + dz * dz
-            ok = (h[2] > 0) & (h[2] < np.inf) & (dd > 0) & (X >= border) & (X <= x_max) & \
-                (Y >= border) & (Y <= y_max)
-            w = np.ones(n, D)
-            if normals is not None:
-                dot = (nx * dx + ny * dy) + nz * dz
-                q = nn * dd
-                dot2 = dot * dot
-                faces_it = (dot > 0) & (dot2 > mc2 * q)
-                ok = ok & (~facing | faces_it)
-                w = np.where(facing, dot2 / q, w)
+            X, Y, dx, dy, dz, dd, ok = project_points(cameras[v], x, y, z, border, x_max, y_max)
+            dot = (nx * dx + ny * dy) + nz * dz
+            q = nn * dd
+            dot2 = dot * dot
+            ok = ok & (~facing | ((dot > 0) & (dot2 > mc2 * q)))
+            w = np.where(facing, dot2 / q, 1.0)
             Xs, Ys = np.where(ok, X, 0.0), np.where(ok, Y, 0.0)
             if depths is not None:
                 zf = np.asarray(depths, F)[v][np.rint(Ys).astype(np.int64),
@@ -131,10 +138,8 @@ def project_colors(points, normals, cameras, images, depths, tol, min_cos, borde
             # (the coordinates of a view that stopped counting at the occlusion test are its own)
             x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
             img = images[v].astype(D)
-            i00, i01, i10, i11 = img[y0, x0], img[y0, x1], img[y1, x0], img[y1, x1]   # [n, C]
-            top = i00 + fx[:, None] * (i01 - i00)
-            bot = i10 + fx[:, None] * (i11 - i10)
-            col = top + fy[:, None] * (bot - top)
+            col = bilerp(img[y0, x0], img[y0, x1], img[y1, x0], img[y1, x1],       # [n, C]
+                         fx[:, None], fy[:, None])
             seen = np.where(ok, seen | np.uint32(1 << v), seen).astype(np.uint32)
             den = np.where(ok, den + w, den)
             num = np.where(ok[:, None], num + w[:, None] * col, num)
@@ -145,6 +150,14 @@ def project_colors(points, normals, cameras, images, depths, tol, min_cos, borde
         out = (blend if mode == 0 else best).astype(F)
         colors = np.where((seen != 0)[:, None], out, F(0)).astype(F)
     return colors, den.astype(F), seen
+
+
+def project_colors(points, normals, cameras, images, depths, tol, min_cos, border, mode):
+    """rn_project_colors: points [n, 3] f32 and normals [n, 3] f32 or None, widened to float64;
+    the rest is observe's."""
+    return observe(np.asarray(points, F).reshape(-1, 3).astype(D),
+                   None if normals is None else np.asarray(normals, F).reshape(-1, 3).astype(D),
+                   cameras, images, depths, tol, min_cos, border, mode)
 
 
 # ------------------------------------------------------------------------------- the inputs

@@ -8,8 +8,9 @@ taken from the kernel.
 """
 import numpy as np
 
-# (the camera rows [V, 15] float64, P row-major | centre, and the camera that looks straight down)
-from appearance_truth import PlaneCamera, pack_cameras  # noqa: F401
+# (the camera rows [V, 15] float64, P row-major | centre, the camera that looks straight down, and
+# the projection of points by one row)
+from appearance_truth import PlaneCamera, pack_cameras, project_points  # noqa: F401
 
 F = np.float32
 D = np.float64
@@ -43,14 +44,7 @@ def integrate(axes, cameras, depths, weights, trunc, border, order=None, sums=Fa
     with np.errstate(all="ignore"):
         x_max, y_max = D(W - 1) - border, D(H - 1) - border
         for v in (range(V) if order is None else order):
-            cam = cameras[v]
-            h = [((cam[4 * k] * x + cam[4 * k + 1] * y) + cam[4 * k + 2] * z) + cam[4 * k + 3]
-                 for k in range(3)]
-            X, Y = h[0] / h[2], h[1] / h[2]
-            dx, dy, dz = cam[12] - x, cam[13] - y, cam[14] - z
-            dd = (dx * dx + dy * dy) + dz * dz
-            ok = (h[2] > 0) & (h[2] < np.inf) & (dd > 0) & (X >= border) & (X <= x_max) & \
-                (Y >= border) & (Y <= y_max)
+            X, Y, _, _, _, dd, ok = project_points(cameras[v], x, y, z, border, x_max, y_max)
             # a view that does not count reads pixel (0, 0)
             xi = np.rint(np.where(ok, X, 0.0)).astype(np.int64)
             yi = np.rint(np.where(ok, Y, 0.0)).astype(np.int64)

@@ -67,11 +67,18 @@ def test_the_kernel_file_is_plain_hip_and_listed():
     for guard in ("rn_app::vertex_in(", "rn_app::corner_in(", "rn_app::clamp_slot(",
                   "rn_app::pixel_in(", "rn_app::image_index(", "rn_app::depth_index("):
         assert guard in src, guard
+    # the names are the shared header's (tests/test_views_cpu.py), under which the bake calls the
+    # per-view step; this kernel keeps it written out (DESIGN.md section 20 says why)
+    assert "rn_view::observe<" not in code and code.count("X = h0 / h2, Y = h1 / h2;") == 1
+    header = open(os.path.join(csrc, "raynet_appearance_args.h")).read()
+    assert "using rn_view::CAMERA_DOUBLES, rn_view::image_index, rn_view::pixel_in;" in header
+    assert "return rn_view::map_index(v, y, x, H, W);" in header        # rn_app::depth_index
     # one instance per channel count
     for c in "1234":
         assert "k_project_colors<%s>" % c in src
     build = inspect.getsource(_lib.build)
     assert '"raynet_appearance.inl"' in build and '"raynet_appearance_args.h"' in build
+    assert '"raynet_views_args.h"' in build
 
 
 def test_launcher_checks_under_sanitizers(tmp_path):

@@ -96,6 +96,28 @@ def test_planted_points_meet_the_conditions_worked_out_by_hand(mode):
     assert scene["depths"][0, 8, 1] == 0 and scene["depths"][0, 8, 3] == 0
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_no_normals_and_zero_normals_are_the_same_bits(plane, mode):
+    """normals=None and an all-zero normal array (of either sign) are one spelling: no facing
+    test, every view weighs 1 -- through project_colors's float32 door and observe's float64 one."""
+    D = np.float64
+    cams, packed, images, depths, pts = plane
+    scene = at.planted_scene()
+    for points, rows, pictures, maps in (
+            (pts, packed, images, depths), (pts, packed, images, None),
+            (scene["points"], scene["cameras"], scene["images"], scene["depths"])):
+        none = at.project_colors(points, None, rows, pictures, maps, TOL, 0.3, 0.5, mode)
+        assert (none[2] != 0).any()
+        for entry, cast in ((at.project_colors, F), (at.observe, D)):
+            for zero in (0.0, -0.0):
+                got = entry(points.astype(cast), np.full(points.shape, zero, cast), rows,
+                            pictures, maps, TOL, 0.3, 0.5, mode)
+                assert np.array_equal(got[0].view(np.int32), none[0].view(np.int32))
+                assert np.array_equal(got[1].view(np.int32), none[1].view(np.int32))
+                assert np.array_equal(got[2], none[2]) and got[2].dtype == np.uint32
+        assert np.array_equal(none[1], np.rint(none[1]))       # whole weights: one per view
+
+
 # ------------------------------------------------------------------------------- the normals
 def _ball():
     belief = it.logistic_ball()

@@ -38,6 +38,8 @@ def test_the_launcher_and_the_kernel_use_these_checks():
                 "rn_fusion::axis_y(", "rn_fusion::axis_z(", "rn_fusion::map_index(",
                 "rn_fusion::pixel_in(", "rn_fusion::voxels(", "rn_fusion::blocks("):
         assert use in code, use
+    assert code.count("rn_view::project(") == 1         # the projection is the shared header's
+    assert "h2" not in code and "cam[" not in code
     # every load of a map goes through the one guarded pixel index
     assert len(re.findall(r"a\.(depths|weights)\[", code)) == 2
     assert len(re.findall(r"a\.(depths|weights)\[pixel\]", code)) == 2

@@ -69,9 +69,19 @@ def test_the_kernels_are_plain_and_use_the_header():
     assert code.count("if (verdict == rn_tex::EMPTY) return RN_OK;") == 2
     for use in ("rn_tex::texel_of_tile(", "rn_tex::texel_of_row(", "rn_tex::owner_of(",
                 "rn_tex::raw_coordinate(", "rn_tex::chart_coordinate(", "rn_tex::texel_index(",
-                "rn_tex::face_in(", "rn_tex::vertex_in(", "rn_tex::layout_of(", "rn_tex::blocks(",
-                "rn_app::image_index(", "rn_app::depth_index(", "rn_app::pixel_in("):
+                "rn_tex::face_in(", "rn_tex::vertex_in(", "rn_tex::layout_of(", "rn_tex::blocks("):
         assert use in code, use
+    # the per-view step is the shared header's, called once; there every image and depth load goes
+    # through image_index / map_index with pixel_in-guarded coordinates, and the bake itself loads
+    # neither
+    assert code.count("rn_view::observe<") == 1 and not re.search(r"a\.(images|depths)\[", code)
+    views = re.sub(r"//.*", "", open(os.path.join(CSRC, "raynet_views_args.h")).read())
+    assert len(re.findall(r"a\.images\[image_index\(", views)) == 4 == views.count("a.images[")
+    assert len(re.findall(r"a\.depths\[map_index\(", views)) == 1 == views.count("a.depths[")
+    for guard in ("pixel_in(yr, a.H) ? yr : 0", "pixel_in(xr, a.W) ? xr : 0",
+                  "x0 = pixel_in(x0, a.W) ? x0 : 0;", "y0 = pixel_in(y0, a.H) ? y0 : 0;",
+                  "std::min(x0 + 1, a.W - 1)", "std::min(y0 + 1, a.H - 1)"):
+        assert views.count(guard) == 1, guard
     assert src.count("constexpr bool TEXTURE_TILED = true;") == 1
     header = open(os.path.join(CSRC, "raynet_texture_args.h")).read()
     hcode = re.sub(r"//.*", "", header)
@@ -79,7 +89,7 @@ def test_the_kernels_are_plain_and_use_the_header():
     assert '#include "raynet_mesh_args.h"' in header and "sizes_ok(nv, nf)" in header
     # the older stages do not know the new one
     for name in ("raynet_appearance.inl", "raynet_render.inl", "raynet_appearance_args.h",
-                 "raynet_render_args.h"):
+                 "raynet_render_args.h", "raynet_views_args.h"):
         assert "texture" not in open(os.path.join(CSRC, name)).read().lower(), name
 
 

@@ -186,6 +186,48 @@ def test_views_behind_the_surface_and_without_the_tests():
     assert not np.array_equal(inside_out[2], want[2])
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_the_corner_texels_of_a_bake_are_rn_project_colors_at_the_vertices(mode):
+    """texture_truth.corner_scene: at a chart's corner the texel's point and normal are the
+    vertex's own, so both entries must give the same bits there -- the one test that would notice
+    the two drifting apart (tests/test_texture_truth.py holds the truths to the same, and the
+    scene to its conditions)."""
+    import torch
+    from raynet_amd import _lib
+    from raynet_amd.hip_implementations.context import _ptr, _stream
+    s = tt.corner_scene()
+    V, Hh, Ww, C = s["images"].shape
+    rc, baked = _bake(s["vertices"], s["faces"], s["L"], s["cameras"], s["images"], s["depths"],
+                      s["normals"], s["tol"], s["min_cos"], s["border"], mode)
+    assert rc == _lib.RN_OK
+    n, Ht, Wt = s["L"].Ht * s["L"].Wt, s["L"].Ht, s["L"].Wt
+    texel = tt.corners_of(s, (baked["texture"][:n].reshape(Ht, Wt, C),
+                              baked["weight"][:n].reshape(Ht, Wt),
+                              baked["views"][:n].view(np.uint32).reshape(Ht, Wt)))
+    ctx = h.ctx()
+    nv = len(s["vertices"])
+    dev = [h.cuda(s[k], t) for k, t in (("vertices", F), ("normals", F), ("cameras", D),
+                                        ("images", F), ("depths", F))]
+    colors, weight = h.padded((nv, C), FILL, torch.float32), h.padded(nv, FILL, torch.float32)
+    views = h.padded(nv, -77, torch.int32)
+    ctx._check(ctx.lib.rn_project_colors(
+        ctx._h, nv, _ptr(dev[0]), _ptr(dev[1]), V, _ptr(dev[2]), Hh, Ww, C, _ptr(dev[3]),
+        _ptr(dev[4]), float(s["tol"]), float(s["min_cos"]), float(s["border"]), int(mode),
+        _ptr(colors), _ptr(weight), _ptr(views), _stream()))
+    order = s["faces"].reshape(-1)
+    vertex = [colors.cpu().numpy()[:nv][order], weight.cpu().numpy()[:nv][order],
+              views.cpu().numpy()[:nv].view(np.uint32)[order]]
+    assert (vertex[2] != 0).all()
+    assert np.array_equal(texel[2], vertex[2])
+    h.assert_same_bits(texel[1], vertex[1], "weight")
+    h.assert_same_bits(texel[0], vertex[0], "colours")
+    # and both are the truth's
+    want = at.project_colors(s["vertices"], s["normals"], s["cameras"], s["images"], s["depths"],
+                             s["tol"], s["min_cos"], s["border"], mode)
+    assert np.array_equal(vertex[2], want[2][order])
+    h.assert_same_bits(vertex[0], want[0][order], "colours against the truth")
+
+
 # ------------------------------------------------------------------------------ b. the lookup
 def _sample(face, bary, L, texture, bilinear):
     import torch

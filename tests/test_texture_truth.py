@@ -233,3 +233,34 @@ def test_the_blend_against_the_best_of_two_views_of_different_obliquity():
     one0 = tt.bake(vertices, faces, L, rows[:1], images[:1], mode=0)[0]
     one1 = tt.bake(vertices, faces, L, rows[:1], images[:1], mode=1)[0]
     assert (one1 == F(0.2)).all() and np.abs(one0 - one1).max() <= np.spacing(F(0.2))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_the_corner_texels_of_a_bake_are_the_colours_of_the_vertices(mode):
+    """At a chart's corner (u, v) is (0, 0), (1, 0) or (0, 1): the texel's point and normal are
+    the vertex's own, so the bake there and project_colors at the vertex are the same bits."""
+    s = tt.corner_scene()
+    views = (s["cameras"], s["images"], s["depths"], s["tol"], s["min_cos"], s["border"], mode)
+    known, point, normal, u, v = tt.texel_points(s["vertices"], s["faces"], s["L"], s["normals"])
+    order = s["faces"].reshape(-1)
+    p, n, cu, cv = tt.corners_of(s, (point, normal, u, v))
+    assert np.array_equal(p, s["vertices"][order].astype(D))
+    assert np.array_equal(n, s["normals"][order].astype(D))
+    assert np.array_equal(np.stack([cu, cv], 1), np.tile([[0, 0], [1, 0], [0, 1]], (2, 1)))
+    baked = tt.corners_of(s, tt.bake(s["vertices"], s["faces"], s["L"], s["cameras"], s["images"],
+                                     s["depths"], s["normals"], s["tol"], s["min_cos"], s["border"],
+                                     mode))
+    colors, weight, seen = at.project_colors(s["vertices"], s["normals"], *views)
+    assert np.array_equal(baked[0].view(I), colors[order].view(I))
+    assert np.array_equal(baked[1].view(I), weight[order].view(I))
+    assert np.array_equal(baked[2], seen[order]) and baked[2].dtype == np.uint32
+    # the comparison is not one of zeros: every corner is seen, one by two views of different
+    # weights, where the blend and the best view differ
+    assert (seen != 0).all()
+    single = [at.project_colors(s["vertices"], s["normals"], s["cameras"][k:k + 1],
+                                s["images"][k:k + 1], s["depths"][k:k + 1], *views[3:])[1]
+              for k in range(3)]
+    two = [i for i in range(4) if ((seen[i] & 3) == 3 and single[0][i] != single[1][i])]
+    assert two
+    other = at.project_colors(s["vertices"], s["normals"], *views[:-1], 1 - mode)[0]
+    assert not np.array_equal(other[two], colors[two])

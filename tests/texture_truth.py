@@ -4,11 +4,12 @@ kernels are held to bit for bit.
 
 The layout is integer arithmetic.  Everything else is np.float64, one ufunc per operation and in
 the definition's order (NumPy fuses nothing), vectorised over the texels per view.  The per-view
-step is rn_project_colors's, written out again here on a float64 point and normal (the texel's
-point is not rounded to float32, so appearance_truth.project_colors, which takes float32 points,
-cannot serve).  Nothing here is taken from the kernels.
+step is rn_project_colors's: appearance_truth.observe on the texel's float64 point and normal,
+neither rounded to float32 on the way.  Nothing here is taken from the kernels.
 """
 import numpy as np
+
+import appearance_truth as at
 
 F = np.float32
 D = np.float64
@@ -131,68 +132,6 @@ def texel_points(vertices, faces, L, normals=None):
     return known, np.where(zero, 0.0, point), np.where(zero, 0.0, normal), u, v
 
 
-def project(points, normal, cameras, images, depths, tol, min_cos, border, mode):
-    """rn_project_colors's definition on float64 points [n, 3] and normals [n, 3] (a zero normal:
-    no facing test, weight 1) -> (colors [n, C] f32, weight [n] f32, views [n] uint32)."""
-    p = np.asarray(points, D).reshape(-1, 3)
-    nr = np.asarray(normal, D).reshape(-1, 3)
-    n = len(p)
-    cameras = np.asarray(cameras, D).reshape(-1, 15)
-    images = np.asarray(images, F)
-    V, H, W, C = images.shape
-    assert len(cameras) == V and 1 <= C <= 4 and 0 <= V <= 32
-    tol, min_cos, border = D(tol), D(min_cos), D(border)
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    with np.errstate(all="ignore"):
-        nx, ny, nz = nr[:, 0], nr[:, 1], nr[:, 2]
-        nn = (nx * nx + ny * ny) + nz * nz
-        facing = nn > 0
-        mc2 = min_cos * min_cos
-        x_max, y_max = D(W - 1) - border, D(H - 1) - border
-        num, best = np.zeros((n, C), D), np.zeros((n, C), D)
-        den, best_w = np.zeros(n, D), np.full(n, -1.0, D)
-        seen = np.zeros(n, np.uint32)
-        for v in range(V):
-            cam = cameras[v]
-            h = [((cam[4 * k] * x + cam[4 * k + 1] * y) + cam[4 * k + 2] * z) + cam[4 * k + 3]
-                 for k in range(3)]
-            X, Y = h[0] / h[2], h[1] / h[2]
-            dx, dy, dz = cam[12] - x, cam[13] - y, cam[14] - z
-            dd = (dx * dx + dy * dy) + dz * dz
-            ok = (h[2] > 0) & (h[2] < np.inf) & (dd > 0) & (X >= border) & (X <= x_max) & \
-                (Y >= border) & (Y <= y_max)
-            dot = (nx * dx + ny * dy) + nz * dz
-            q = nn * dd
-            dot2 = dot * dot
-            ok = ok & (~facing | ((dot > 0) & (dot2 > mc2 * q)))
-            w = np.where(facing, dot2 / q, 1.0)
-            Xs, Ys = np.where(ok, X, 0.0), np.where(ok, Y, 0.0)
-            if depths is not None:
-                zf = np.asarray(depths, F)[v][np.rint(Ys).astype(np.int64),
-                                              np.rint(Xs).astype(np.int64)]
-                lim = zf.astype(D) + tol
-                ok = ok & (zf > 0) & (dd <= lim * lim)
-            xf, yf = np.floor(Xs), np.floor(Ys)
-            fx, fy = Xs - xf, Ys - yf
-            x0, y0 = xf.astype(np.int64), yf.astype(np.int64)
-            x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
-            img = images[v].astype(D)
-            i00, i01, i10, i11 = img[y0, x0], img[y0, x1], img[y1, x0], img[y1, x1]
-            top = i00 + fx[:, None] * (i01 - i00)
-            bot = i10 + fx[:, None] * (i11 - i10)
-            col = top + fy[:, None] * (bot - top)
-            seen = np.where(ok, seen | np.uint32(1 << v), seen).astype(np.uint32)
-            den = np.where(ok, den + w, den)
-            num = np.where(ok[:, None], num + w[:, None] * col, num)
-            better = ok & (w > best_w)
-            best_w = np.where(better, w, best_w)
-            best = np.where(better[:, None], col, best)
-        blend = num / den[:, None]
-        out = (blend if mode == 0 else best).astype(F)
-        colors = np.where((seen != 0)[:, None], out, F(0)).astype(F)
-    return colors, den.astype(F), seen
-
-
 def bake(vertices, faces, L, cameras, images, depths=None, normals=None, tol=0.0, min_cos=0.0,
          border=0.0, mode=0):
     """-> (texture [Ht, Wt, C] f32, weight [Ht, Wt] f32, views [Ht, Wt] uint32).  cameras [V, 15]
@@ -201,8 +140,8 @@ def bake(vertices, faces, L, cameras, images, depths=None, normals=None, tol=0.0
     images = np.asarray(images, F)
     C = images.shape[3]
     known, point, normal, _, _ = texel_points(vertices, faces, L, normals)
-    colors, weight, views = project(point.reshape(-1, 3), normal.reshape(-1, 3), cameras, images,
-                                    depths, tol, min_cos, border, mode)
+    colors, weight, views = at.observe(point.reshape(-1, 3), normal.reshape(-1, 3), cameras, images,
+                                       depths, tol, min_cos, border, mode)
     k = known.reshape(-1)
     texture = np.where(k[:, None], colors, F(0)).astype(F).reshape(L.Ht, L.Wt, C)
     weight = np.where(k, weight, F(0)).astype(F).reshape(L.Ht, L.Wt)
@@ -233,10 +172,33 @@ def sample(face, bary, L, texture, bilinear=True):
         fx, fy = x - xf, y - yf
         x0, y0 = xf.astype(np.int64), yf.astype(np.int64)
         x1, y1 = np.minimum(x0 + 1, L.Wt - 1), np.minimum(y0 + 1, L.Ht - 1)
-        t00, t01, t10, t11 = tex[y0, x0], tex[y0, x1], tex[y1, x0], tex[y1, x1]
-        top = t00 + fx[:, None] * (t01 - t00)
-        bot = t10 + fx[:, None] * (t11 - t10)
-        out = (top + fy[:, None] * (bot - top)).astype(F)
+        out = at.bilerp(tex[y0, x0], tex[y0, x1], tex[y1, x0], tex[y1, x1], fx[:, None],
+                        fy[:, None]).astype(F)
     else:
         out = texture[np.rint(y).astype(np.int64), np.rint(x).astype(np.int64)]
     return np.where(known[:, None], out, F(0)).astype(F).reshape(shape + (C,))
+
+
+# ------------------------------------------------------------------------------- the inputs
+def corner_scene():
+    """Two faces (one cell: the lower and the upper chart) just off the plane of
+    appearance_truth.plane_scene, T = 4, its three 24 x 32 x 3 views with their depth maps, vertex
+    normals that lean, and no vertex or normal component equal to zero: at a chart's corner texel
+    (u, v) is (0, 0), (1, 0) or (0, 1), so the texel's point and normal are the vertex's own,
+    exactly (0 a + b meets no signed zero), and the bake there is rn_project_colors at the vertex."""
+    cams, images, depths = at.plane_scene()
+    vertices = np.array([[-0.7, -0.6, 0.02], [0.8, -0.5, -0.03], [0.75, 0.65, 0.04],
+                         [-0.65, 0.7, -0.02]], F)
+    faces = np.array([[0, 1, 2], [0, 2, 3]], I)
+    normals = np.array([[0.1, -0.15, 1.0], [-0.2, 0.05, 0.9], [0.3, 0.25, 1.1], [-0.05, -0.3, 0.8]], F)
+    assert (vertices != 0).all() and (normals != 0).all()
+    return dict(vertices=vertices, faces=faces, normals=normals, L=Layout(2, 4),
+                cameras=at.pack_cameras(cams), images=images, depths=depths, tol=0.1, min_cos=0.1,
+                border=0.5)
+
+
+def corners_of(scene, planes):
+    """The rows of baked planes [Ht, Wt, ...] at the corner texels of every face, in the order
+    of scene["faces"].reshape(-1)."""
+    at_ = np.concatenate([corner_texels(scene["L"], f) for f in range(len(scene["faces"]))])
+    return [np.asarray(p)[at_[:, 1], at_[:, 0]] for p in planes]
