@@ -31,35 +31,20 @@ class RaynetHipError(RuntimeError):
     pass
 
 
+def sources():
+    """What the library is built from, the translation unit first: raynet_hip.hip, every *.inl and
+    *.h of csrc/ (the unit includes them all) and the public header.  build() compares their
+    times with the library's; a new kernel file is a source by being there."""
+    included = sorted(f for f in os.listdir(CSRC) if f.endswith((".inl", ".h")))
+    return [os.path.join(CSRC, f) for f in ["raynet_hip.hip"] + included] + [HEADER]
+
+
 def build(force=False, verbose=False, extra_flags=(), out=None):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).
     extra_flags / out: a VARIANT build (A/B runs, the exact-arithmetic build of the tests) into
     another path; the flags end up in rn_version() (RN_BUILD_EXTRA), so a variant can never
     pass for the shipped library (tests/test_abi.py)."""
-    srcs = [os.path.join(CSRC, "raynet_hip.hip"), os.path.join(CSRC, "raynet_kernels.h"),
-            os.path.join(CSRC, "raynet_launch.inl"), os.path.join(CSRC, "raynet_box_policy.h"),
-            os.path.join(CSRC, "raynet_prepare.inl"), os.path.join(CSRC, "raynet_mrf.inl"),
-            os.path.join(CSRC, "raynet_train.inl"), os.path.join(CSRC, "raynet_eval.inl"),
-            os.path.join(CSRC, "raynet_mesh.inl"), os.path.join(CSRC, "raynet_filters.inl"),
-            os.path.join(CSRC, "raynet_cloud.inl"), os.path.join(CSRC, "raynet_batch.inl"),
-            os.path.join(CSRC, "raynet_volume.inl"), os.path.join(CSRC, "raynet_volume_args.h"),
-            os.path.join(CSRC, "raynet_isosurface.inl"),
-            os.path.join(CSRC, "raynet_isosurface_args.h"),
-            os.path.join(CSRC, "raynet_appearance.inl"),
-            os.path.join(CSRC, "raynet_appearance_args.h"),
-            os.path.join(CSRC, "raynet_fusion.inl"), os.path.join(CSRC, "raynet_fusion_args.h"),
-            os.path.join(CSRC, "raynet_components.inl"),
-            os.path.join(CSRC, "raynet_components_args.h"),
-            os.path.join(CSRC, "raynet_smooth.inl"), os.path.join(CSRC, "raynet_smooth_args.h"),
-            os.path.join(CSRC, "raynet_simplify.inl"),
-            os.path.join(CSRC, "raynet_simplify_args.h"),
-            os.path.join(CSRC, "raynet_quadric.inl"), os.path.join(CSRC, "raynet_quadric_args.h"),
-            os.path.join(CSRC, "raynet_holes.inl"), os.path.join(CSRC, "raynet_holes_args.h"),
-            os.path.join(CSRC, "raynet_mesh_args.h"), os.path.join(CSRC, "raynet_views_args.h"),
-            os.path.join(CSRC, "raynet_render.inl"), os.path.join(CSRC, "raynet_render_args.h"),
-            os.path.join(CSRC, "raynet_scan.inl"), os.path.join(CSRC, "raynet_scan_args.h"),
-            os.path.join(CSRC, "raynet_texture.inl"), os.path.join(CSRC, "raynet_texture_args.h"),
-            HEADER]
+    srcs = sources()
     extra = list(extra_flags) + os.environ.get("RAYNET_HIPCC_EXTRA", "").split()
     if out is None and ENV_LIB:
         # RAYNET_HIP_LIB names ANOTHER build of the library (a variant somebody made on purpose):
@@ -139,8 +124,8 @@ _L = ctypes.c_int64
 _F = ctypes.c_float
 _D = ctypes.c_double
 
-# name -> argtypes; mirrors include/raynet_hip.h one to one (checked by
-# tests/test_abi.py against the header text)
+# name -> argtypes; mirrors include/raynet_hip.h one to one (tests/test_abi.py checks every
+# entry, its return type included, against the header text and the loaded library)
 SIGNATURES = {
     "rn_create": [ctypes.POINTER(Config), ctypes.POINTER(_P)],
     "rn_destroy": [_P],
@@ -250,6 +235,20 @@ SIGNATURES = {
     "rn_timer_stop": [_P, _P, ctypes.POINTER(_F)],
 }
 
+# name -> restype of the entries that do not return an rn_status int
+RETURNS = {
+    "rn_destroy": None,
+    "rn_last_error": ctypes.c_char_p,
+    "rn_version": ctypes.c_char_p,
+    "rn_acc_size": _L,
+    "rn_slab_boxes_size": _L,
+    "rn_isosurface_workspace_bytes": _L,
+    "rn_mesh_smooth_workspace_bytes": _L,
+    "rn_mesh_simplify_workspace_bytes": _L,
+    "rn_mesh_place_quadric_workspace_bytes": _L,
+    "rn_mesh_fill_holes_workspace_bytes": _L,
+}
+
 _lib = None
 
 
@@ -270,16 +269,6 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    lib.rn_destroy.restype = None
-    lib.rn_last_error.restype = ctypes.c_char_p
-    lib.rn_version.restype = ctypes.c_char_p
-    lib.rn_acc_size.restype = ctypes.c_int64
-    lib.rn_slab_boxes_size.restype = ctypes.c_int64
-    lib.rn_isosurface_workspace_bytes.restype = ctypes.c_int64
-    lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64
-    lib.rn_mesh_simplify_workspace_bytes.restype = ctypes.c_int64
-    lib.rn_mesh_place_quadric_workspace_bytes.restype = ctypes.c_int64
-    lib.rn_mesh_fill_holes_workspace_bytes.restype = ctypes.c_int64
+        fn.restype = RETURNS.get(name, ctypes.c_int)
     _lib = lib
     return lib

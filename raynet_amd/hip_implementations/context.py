@@ -75,19 +75,66 @@ def _workspace(workspace, need, device):
     return _chk(workspace, torch.uint8, need, "workspace", align=8)
 
 
-def _three_ints(x, name):
-    """Three whole numbers of a host array argument (dims), each an int32."""
-    a = np.asarray(x)
-    if a.shape != (3,) or not np.all(a == np.floor(a)) or np.any(np.abs(a) >= 2 ** 31):
-        raise ValueError("%s: three whole numbers, got %r" % (name, x))
-    return [int(v) for v in a]
+def _table(t, k, dtype, name, align=4, rows=None):
+    """A table as the entries take one: a 2-D tensor of `k` columns (and, if given, exactly `rows`
+    rows) that passes _chk -> its row count."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != k or \
+            rows is not None and t.shape[0] != rows:
+        raise ValueError("%s: expected a (%s, %d) tensor, got %s" % (
+            name, "n" if rows is None else rows, k,
+            tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    n = int(t.shape[0])
+    _chk(t, dtype, k * n, name, align=align)
+    return n
 
 
-def _three_floats(x, name):
+def _stack(t, V, name, channels=False):
+    """A stack of float32 maps (V, H, W) or, with channels, of images (V, H, W, C), V given or
+    (None) the stack's own -> its shape."""
+    dims = 4 if channels else 3
+    if not isinstance(t, torch.Tensor) or t.dim() != dims or V is not None and t.shape[0] != V:
+        raise ValueError("%s: expected (%s, H, W%s), got %s" % (
+            name, "V" if V is None else V, ", C" if channels else "",
+            tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    _chk(t, torch.float32, t.numel(), name)
+    return tuple(int(s) for s in t.shape)
+
+
+def _atlas_texels(n_faces, T, cells_per_row):
+    """Texels of the atlas of n_faces faces, T steps per leg, cells_per_row cells per row (two
+    faces share a cell of (T + 5)^2); 0 for the sizes the entries refuse themselves."""
+    if not (1 <= T <= 1024 and 1 <= cells_per_row <= 16384 and n_faces >= 0):
+        return 0
+    cell_rows = ((n_faces + 1) // 2 + cells_per_row - 1) // cells_per_row
+    return cells_per_row * (T + 5) * cell_rows * (T + 5)
+
+
+def _host3(x, ctype, name):
+    """Three host numbers as the array an entry takes for `const T name[3]`: whole int32 numbers
+    for c_int32, any numbers for c_double."""
+    if ctype is ctypes.c_int32:
+        a = np.asarray(x)
+        if a.shape != (3,) or not np.all(a == np.floor(a)) or np.any(np.abs(a) >= 2 ** 31):
+            raise ValueError("%s: three whole numbers, got %r" % (name, x))
+        return (ctype * 3)(*[int(v) for v in a])
     a = np.asarray(x, np.float64)
     if a.shape != (3,):
         raise ValueError("%s: three numbers, got %r" % (name, x))
-    return [float(v) for v in a]
+    return (ctype * 3)(*[float(v) for v in a])
+
+
+def _size(answer, entry, **sizes):
+    """A size entry's answer, or a ValueError naming its arguments (the entries answer -1)."""
+    if answer < 0:
+        raise ValueError("%s: bad sizes (%s)" % (entry, ", ".join("%s %s" % s for s in sizes.items())))
+    return int(answer)
+
+
+def _chk_centers(center, n, rays_per_center, optional=False):
+    """The centres of the depth sweeps: one [3] for all n rays or, with rays_per_center > 0, a
+    table [groups][4] of one per group of that many rays."""
+    need = 4 * ((n + rays_per_center - 1) // rays_per_center) if rays_per_center > 0 else 3
+    _chk(center, torch.float32, need, "center", optional=optional, align=4)
 
 
 SCATTER_ITEM_TILES = 1 << 19      # tiles an int32 item `tile << 12 | ...` can name
@@ -173,8 +220,18 @@ class HipContext(object):
         if rc != _lib.RN_OK:
             raise _lib.RaynetHipError("rn_create failed: %s" % _lib.STATUS.get(rc, rc))
         self._h = handle
+        self._options = None            # the rn_options last applied (set_options)
+        # what the context keeps alive, or knows about the bindings the library holds pointers of
         self._grid_set = False
-        self._options = None
+        self._vg_keepalive = None       # the voxel centres rn_set_voxel_grid was given
+        self._grid_src = None           # the caller's array they were made from (the K-API drivers)
+        self._slab_boxes = None         # (table, vox) of bind_slab_boxes
+        self._scatter_items = None      # (items, vox, level) of bind_scatter_items
+        self._seg_scratch = None        # [rows][8] f32 the traversal leaves the rays' segments in
+        # profiling (prof_begin / prof_end)
+        self._prof_cap = 0
+        self.prof_active = False        # event pairs around launches: such a pass is not captured
+        self.prof_starts = []
 
     def set_options(self, options):
         """Apply a PathOptions' context half (rn_options); a no-op when nothing changed."""
@@ -260,20 +317,12 @@ class HipContext(object):
                                                          _ptr(items), int(items.numel())))
         return items
 
-    def _drop_foreign_items(self, vox):
-        """A work list bound for another tensor must not meet a launch whose buffer happens to sit
-        at the address (and have the row count) the list was built for: unbind unless `vox` IS the
-        tensor it describes."""
-        cur = getattr(self, "_scatter_items", None)
-        if cur is not None and cur[1] is not vox:
-            self.bind_scatter_items(None)
-
     def scatter_items_bound(self, items):
-        cur = getattr(self, "_scatter_items", None)
+        cur = self._scatter_items
         return cur is not None and cur[0] is items
 
     def slab_boxes_bound_to(self, vox):
-        sb = getattr(self, "_slab_boxes", None)
+        sb = self._slab_boxes
         return sb is not None and sb[1] is vox
 
     def scatter_state(self):
@@ -393,20 +442,15 @@ class HipContext(object):
         """rn_project_colors: points (n, 3) f32, normals (n, 3) f32 or None, cameras (V, 15) f64,
         images (V, H, W, C) f32, depths (V, H, W) f32 or None -> colors (>= n, C) f32, weight
         [>= n] f32, views [>= n] int32 (the bits of the u32 mask); mode 0: blend, 1: best."""
-        n, V = len(points), len(cameras)
-        if images.dim() != 4 or images.shape[0] != V:
-            raise ValueError("images: expected (%d, H, W, C), got %s" % (V, tuple(images.shape)))
-        H, W, C = (int(s) for s in images.shape[1:])
+        n = len(points)
+        V = _table(cameras, 15, torch.float64, "cameras", align=8)
+        _, H, W, C = _stack(images, V, "images", channels=True)
         _chk(points, torch.float32, 3 * n, "points")
         _chk(normals, torch.float32, 3 * n, "normals", optional=True)
-        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
-        _chk(images, torch.float32, V * H * W * C, "images")
         _chk(depths, torch.float32, V * H * W, "depths", optional=True)
         _chk(colors, torch.float32, n * C, "colors")
         _chk(weight, torch.float32, n, "weight")
         _chk(views, torch.int32, n, "views")
-        if cameras.dim() != 2 or cameras.shape[1] != 15:
-            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
         self._check(self.lib.rn_project_colors(
             self._h, n, _ptr(points), _ptr(normals), V, _ptr(cameras), H, W, C, _ptr(images),
             _ptr(depths), float(tol), float(min_cos), float(border), int(mode), _ptr(colors),
@@ -418,15 +462,11 @@ class HipContext(object):
         centres, weights (V, H, W) f32 or None -> (tsdf, weight), both [gx][gy][gz] f32 over the
         context's grid: the weighted mean of the views' truncated signed distances (in units of
         `trunc`, 1 in free space) and the sum of their weights; 1 and 0 where no view counts."""
-        if depths.dim() != 3 or weights is not None and weights.shape != depths.shape:
-            raise ValueError("depths: expected (V, H, W) and weights of the same shape, got %s, %s"
-                             % (tuple(depths.shape), None if weights is None else tuple(weights.shape)))
-        V, H, W = (int(s) for s in depths.shape)
-        if cameras.dim() != 2 or tuple(cameras.shape) != (V, 15):
-            raise ValueError("cameras: expected (%d, 15), got %s" % (V, tuple(cameras.shape)))
-        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
-        _chk(depths, torch.float32, V * H * W, "depths")
-        _chk(weights, torch.float32, V * H * W, "weights", optional=True)
+        V, H, W = _stack(depths, None, "depths")
+        if weights is not None and _stack(weights, V, "weights") != (V, H, W):
+            raise ValueError("weights: expected the shape of depths %s, got %s"
+                             % ((V, H, W), tuple(weights.shape)))
+        _table(cameras, 15, torch.float64, "cameras", align=8, rows=V)
         if tsdf is None:
             tsdf = torch.empty(self.grid_shape, dtype=torch.float32, device=depths.device)
         if weight is None:
@@ -449,11 +489,7 @@ class HipContext(object):
         nv = int(n_vertices)
         if nv < 0:
             raise ValueError("n_vertices: 0 or more, got %d" % nv)
-        if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
-            raise ValueError("faces: expected a (nf, 3) tensor, got %s" % (
-                tuple(faces.shape) if isinstance(faces, torch.Tensor) else type(faces).__name__,))
-        nf = len(faces)
-        _chk(faces, torch.int32, 3 * nf, "faces")
+        nf = _table(faces, 3, torch.int32, "faces")
         outs = []
         for t, name in ((labels, "labels"), (vertex_counts, "vertex_counts"),
                         (face_counts, "face_counts")):
@@ -472,10 +508,8 @@ class HipContext(object):
     # ---- Taubin smoothing of a mesh (raynet_amd/smoothing.py) ---------------------------------
     def mesh_smooth_workspace_bytes(self, nv, nf):
         """rn_mesh_smooth_workspace_bytes: the bytes rn_mesh_smooth needs for nv vertices, nf faces."""
-        n = int(self.lib.rn_mesh_smooth_workspace_bytes(self._h, int(nv), int(nf)))
-        if n < 0:
-            raise ValueError("rn_mesh_smooth_workspace_bytes: bad sizes (nv %d, nf %d)" % (nv, nf))
-        return n
+        return _size(self.lib.rn_mesh_smooth_workspace_bytes(self._h, int(nv), int(nf)),
+                     "rn_mesh_smooth_workspace_bytes", nv=nv, nf=nf)
 
     def mesh_smooth(self, vertices, faces, offsets, corners, fixed=None, iterations=10, lam=0.5,
                     mu=-0.53, max_move=float("inf"), workspace=None, out=None):
@@ -501,12 +535,9 @@ class HipContext(object):
     def mesh_simplify_workspace_bytes(self, nv, nf, dims):
         """rn_mesh_simplify_workspace_bytes: the bytes rn_mesh_simplify needs for nv vertices, nf
         faces and a grid of dims[0] x dims[1] x dims[2] cells (32 bytes per cell)."""
-        d = (ctypes.c_int32 * 3)(*_three_ints(dims, "dims"))
-        n = int(self.lib.rn_mesh_simplify_workspace_bytes(int(nv), int(nf), d))
-        if n < 0:
-            raise ValueError("rn_mesh_simplify_workspace_bytes: bad sizes (nv %d, nf %d, dims %s)"
-                             % (nv, nf, tuple(d)))
-        return n
+        d = _host3(dims, ctypes.c_int32, "dims")
+        return _size(self.lib.rn_mesh_simplify_workspace_bytes(int(nv), int(nf), d),
+                     "rn_mesh_simplify_workspace_bytes", nv=nv, nf=nf, dims=tuple(d))
 
     def mesh_simplify(self, vertices, faces, origin, cell, dims, workspace=None):
         """rn_mesh_simplify: vertices (nv, 3) f32, faces (nf, 3) i32, the grid (origin [3], cell
@@ -517,9 +548,9 @@ class HipContext(object):
         8-byte aligned (allocated if None).  Synchronises the stream once: the two counts come
         back to slice the outputs."""
         nv, nf = _chk_mesh(vertices, faces)
-        d = (ctypes.c_int32 * 3)(*_three_ints(dims, "dims"))
-        o = (ctypes.c_double * 3)(*_three_floats(origin, "origin"))
-        c = (ctypes.c_double * 3)(*_three_floats(cell, "cell"))
+        d = _host3(dims, ctypes.c_int32, "dims")
+        o = _host3(origin, ctypes.c_double, "origin")
+        c = _host3(cell, ctypes.c_double, "cell")
         need = self.mesh_simplify_workspace_bytes(nv, nf, dims)
         workspace = _workspace(workspace, need, vertices.device)
         device = vertices.device
@@ -538,11 +569,8 @@ class HipContext(object):
     def mesh_place_quadric_workspace_bytes(self, nv, nf, nvo):
         """rn_mesh_place_quadric_workspace_bytes: the bytes rn_mesh_place_quadric needs for nv
         input vertices, nf input faces and nvo output vertices (88 per output vertex)."""
-        n = int(self.lib.rn_mesh_place_quadric_workspace_bytes(int(nv), int(nf), int(nvo)))
-        if n < 0:
-            raise ValueError("rn_mesh_place_quadric_workspace_bytes: bad sizes (nv %d, nf %d, "
-                             "nvo %d)" % (nv, nf, nvo))
-        return n
+        return _size(self.lib.rn_mesh_place_quadric_workspace_bytes(int(nv), int(nf), int(nvo)),
+                     "rn_mesh_place_quadric_workspace_bytes", nv=nv, nf=nf, nvo=nvo)
 
     def mesh_place_quadric(self, vertices, faces, cluster, positions, cell, regularization=2.0 ** -10,
                            max_move=1.0, workspace=None, out=None):
@@ -558,15 +586,10 @@ class HipContext(object):
         One read-back: the counts."""
         nv, nf = _chk_mesh(vertices, faces)
         _chk(cluster, torch.int32, nv, "cluster")
-        if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
-            raise ValueError("positions: expected a (nvo, 3) tensor, got %s" % (
-                tuple(positions.shape) if isinstance(positions, torch.Tensor)
-                else type(positions).__name__,))
-        nvo = len(positions)
-        _chk(positions, torch.float32, 3 * nvo, "positions")
+        nvo = _table(positions, 3, torch.float32, "positions")
         if nvo > nv:
             raise ValueError("positions: at most the %d rows of vertices, got %d" % (nv, nvo))
-        c = (ctypes.c_double * 3)(*_three_floats(cell, "cell"))
+        c = _host3(cell, ctypes.c_double, "cell")
         need = self.mesh_place_quadric_workspace_bytes(nv, nf, nvo)
         workspace = _workspace(workspace, need, vertices.device)
         if out is None:
@@ -583,10 +606,8 @@ class HipContext(object):
     def mesh_fill_holes_workspace_bytes(self, nv, nf):
         """rn_mesh_fill_holes_workspace_bytes: the bytes rn_mesh_fill_holes needs for nv vertices
         and nf faces."""
-        n = int(self.lib.rn_mesh_fill_holes_workspace_bytes(int(nv), int(nf)))
-        if n < 0:
-            raise ValueError("rn_mesh_fill_holes_workspace_bytes: bad sizes (nv %d, nf %d)" % (nv, nf))
-        return n
+        return _size(self.lib.rn_mesh_fill_holes_workspace_bytes(int(nv), int(nf)),
+                     "rn_mesh_fill_holes_workspace_bytes", nv=nv, nf=nf)
 
     def mesh_fill_holes(self, vertices, faces, offsets, corners, max_edges, workspace=None):
         """rn_mesh_fill_holes: vertices (nv, 3) f32, faces (nf, 3) i32, the corner table (offsets
@@ -709,12 +730,8 @@ class HipContext(object):
     def nearest_neighbors(self, ref_xyzw, query_xyzw, dist, idx=None):
         """ref_xyzw (n_ref, 4) f32, query_xyzw (n_query, 4) f32 (the fourth lane is not read) ->
         dist [n_query] f32 and / or idx [n_query] i32 (either may be None, not both)."""
-        for name, t in (("ref_xyzw", ref_xyzw), ("query_xyzw", query_xyzw)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 4:
-                raise ValueError("%s: expected shape (n, 4), got %s"
-                                 % (name, tuple(getattr(t, "shape", ())),))
-            _chk(t, torch.float32, 4 * int(t.shape[0]), name, align=16)
-        n_ref, n_query = int(ref_xyzw.shape[0]), int(query_xyzw.shape[0])
+        n_ref = _table(ref_xyzw, 4, torch.float32, "ref_xyzw", align=16)
+        n_query = _table(query_xyzw, 4, torch.float32, "query_xyzw", align=16)
         if dist is None and idx is None:
             raise ValueError("dist, idx: at least one output is required")
         _chk(dist, torch.float32, n_query, "dist", optional=True)
@@ -766,17 +783,14 @@ class HipContext(object):
         """points (n, 3) f32, cameras (V, 21) f64 (K | R | t), zbuf (V, H, W) i32 holding float
         bit patterns, filled with 0x7F800000 by the caller; counts: None or [2] i64, zeroed
         (landed pairs | atomics the pre-test skipped)."""
-        n, V, H, W = points.shape[0], cameras.shape[0], int(H), int(W)
+        H, W = int(H), int(W)
         if H < 1 or W < 1:
             raise ValueError("H, W: at least 1, got %d, %d" % (H, W))
+        n = _table(points, 3, torch.float32, "points")
+        V = _table(cameras, 21, torch.float64, "cameras", align=8)
         if n > (1 << 30):
             raise ValueError("points: at most 2^30 per call, got %d" % n)
-        _chk(points, torch.float32, 3 * n, "points")
-        _chk(cameras, torch.float64, 21 * V, "cameras", align=8)
         _chk(zbuf, torch.int32, V * H * W, "zbuf")
-        if tuple(points.shape) != (n, 3) or tuple(cameras.shape) != (V, 21):
-            raise ValueError("points (n, 3) and cameras (V, 21): got %s, %s"
-                             % (tuple(points.shape), tuple(cameras.shape)))
         if counts is None:
             self._check(self.lib.rn_cloud_zbuffer(self._h, n, _ptr(points), V, _ptr(cameras), H, W,
                                                   _ptr(zbuf), _stream()))
@@ -814,9 +828,7 @@ class HipContext(object):
             raise ValueError("n * N * D = %d: at most 2^30 per call" % (n * N * self.D))
         _chk(ray_idxs, torch.int32, n, "ray_idxs")
         _chk(depth, torch.float32, n, "depth")
-        _chk(cams, torch.float32, V * self.BATCH_CAMERA_FLOATS, "cams")
-        if tuple(cams.shape) != (V, self.BATCH_CAMERA_FLOATS):
-            raise ValueError("cams: expected shape (%d, 28), got %s" % (V, tuple(cams.shape)))
+        _table(cams, self.BATCH_CAMERA_FLOATS, torch.float32, "cams", rows=V)
         _chk(points, torch.float32, n * self.D * 4, "points", align=16)
         _chk(target, torch.float32, n * 4, "target", align=16)
         _chk(centres, torch.int32, n * N * self.D * 2, "centres", align=8)
@@ -935,10 +947,7 @@ class HipContext(object):
         Moeller-Trumbore (u, v) and the attributes interpolated there; 0 on a miss."""
         nv, nf = _chk_mesh(vertices, faces)
         H, W = int(H), int(W)
-        if cameras.dim() != 2 or cameras.shape[1] != 15:
-            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
-        V = int(cameras.shape[0])
-        _chk(cameras, torch.float32, 15 * V, "cameras")
+        V = _table(cameras, 15, torch.float32, "cameras")
         _chk(nodes, torch.float32, 16 * max(nf - 1, 1), "nodes", align=16)
         _chk(leaves, torch.float32, 12 * nf, "leaves", align=16)
         C = 0
@@ -949,9 +958,7 @@ class HipContext(object):
             C = int(colors.shape[1])
             _chk(colors, torch.float32, nv * C, "colors")
         if normals is not None:
-            if tuple(normals.shape) != (nv, 3):
-                raise ValueError("normals: expected (%d, 3), got %s" % (nv, tuple(normals.shape)))
-            _chk(normals, torch.float32, 3 * nv, "normals")
+            _table(normals, 3, torch.float32, "normals", rows=nv)
         device = vertices.device
         face = torch.empty((V, H, W), dtype=torch.int32, device=device)
         depth = torch.empty((V, H, W), dtype=torch.float32, device=device)
@@ -975,18 +982,11 @@ class HipContext(object):
         mask) of the atlas of T steps per leg and cells_per_row cells per row; mode 0: blend, 1:
         best."""
         nv, nf = _chk_mesh(vertices, faces)
-        T, Cw, V = int(T), int(cells_per_row), len(cameras)
-        if images.dim() != 4 or images.shape[0] != V:
-            raise ValueError("images: expected (%d, H, W, C), got %s" % (V, tuple(images.shape)))
-        H, W, C = (int(s) for s in images.shape[1:])
-        if cameras.dim() != 2 or cameras.shape[1] != 15:
-            raise ValueError("cameras: expected (V, 15), got %s" % (tuple(cameras.shape),))
-        texels = 0
-        if 1 <= T <= 1024 and 1 <= Cw <= 16384:         # (else the entry refuses)
-            texels = Cw * (T + 5) * (((nf + 1) // 2 + Cw - 1) // Cw) * (T + 5)
+        T, Cw = int(T), int(cells_per_row)
+        V = _table(cameras, 15, torch.float64, "cameras", align=8)
+        _, H, W, C = _stack(images, V, "images", channels=True)
+        texels = _atlas_texels(nf, T, Cw)
         _chk(normals, torch.float32, 3 * nv, "normals", optional=True)
-        _chk(cameras, torch.float64, 15 * V, "cameras", align=8)
-        _chk(images, torch.float32, V * H * W * C, "images")
         _chk(depths, torch.float32, V * H * W, "depths", optional=True)
         _chk(texture, torch.float32, texels * C, "texture")
         _chk(weight, torch.float32, texels, "weight")
@@ -1007,9 +1007,7 @@ class HipContext(object):
                              % (tuple(texture.shape),))
         C = int(texture.shape[2])
         nf, T, Cw = int(n_faces), int(T), int(cells_per_row)
-        texels = 0
-        if 1 <= T <= 1024 and 1 <= Cw <= 16384 and nf >= 0:
-            texels = Cw * (T + 5) * (((nf + 1) // 2 + Cw - 1) // Cw) * (T + 5)
+        texels = _atlas_texels(nf, T, Cw)
         _chk(face, torch.int32, n, "face")
         _chk(bary, torch.float32, 2 * n, "bary")
         _chk(texture, torch.float32, texels * C, "texture")
@@ -1028,7 +1026,7 @@ class HipContext(object):
                 mask |= 1 << ids[name]
         self._check(self.lib.rn_prof_select(self._h, mask))
         self._prof_cap = capacity
-        self.prof_active = True       # (event pairs around launches: such a pass is not captured)
+        self.prof_active = True
         self._check(self.lib.rn_prof_begin(self._h, capacity))
 
     def prof_end(self):
@@ -1209,7 +1207,7 @@ class HipContext(object):
     # -- resident-scene path ---------------------------------------------------
     def _segments(self, rows):
         """Scratch for the rays' bbox entry / exit points ([rows][8] f32), kept per context."""
-        seg = getattr(self, "_seg_scratch", None)
+        seg = self._seg_scratch
         if seg is None or seg.shape[0] < rows:
             seg = torch.empty((rows, 8), dtype=torch.float32, device=self.device)
             self._seg_scratch = seg
@@ -1235,20 +1233,27 @@ class HipContext(object):
                                               _ptr(rvc), _ptr(Sr),
                                               _ptr(self._segments(n)), _stream()))
 
-    def scene_prepare_all(self, n_images, rows_per_image, ray_idxs, feature_table, cameras, vox,
-                          rvc, Sr, order=None):
-        """feature_table: int64 CUDA tensor [n_images, N] of device pointers;
-        cameras: float32 CUDA tensor [n_images, 12N + 16]."""
+    def _chk_scene(self, n_images, rows_per_image, ray_idxs, feature_table, cameras, vox, rvc, Sr,
+                   order):
+        """What scene_prepare_all and a scene plan take alike: feature_table, an int64 CUDA tensor
+        [n_images, N] of device pointers; cameras, float32 [n_images, 12N + 16]; the rays and
+        their schedule [n]; the row arrays of all images -> (n, rows)."""
         n, rows = len(ray_idxs), int(n_images) * int(rows_per_image)
-        f32, i32 = torch.float32, torch.int32
+        f32, i32, ra = torch.float32, torch.int32, self._row_align
         _chk(feature_table, torch.int64, n_images * self.N, "feature_table", align=8)
         assert tuple(feature_table.shape) == (n_images, self.N)
         _chk(cameras, f32, n_images * (12 * self.N + 16), "cameras")
         assert tuple(cameras.shape) == (n_images, 12 * self.N + 16)
         _chk(ray_idxs, i32, n, "ray_idxs"); _chk(order, i32, n, "order", optional=True)
-        ra = self._row_align
         _chk(vox, i32, rows * self.M, "vox", align=ra); _chk(rvc, i32, rows, "rvc")
         _chk(Sr, f32, rows * self.M, "Sr", align=ra)
+        return n, rows
+
+    def scene_prepare_all(self, n_images, rows_per_image, ray_idxs, feature_table, cameras, vox,
+                          rvc, Sr, order=None):
+        """feature_table, cameras: see _chk_scene."""
+        n, rows = self._chk_scene(n_images, rows_per_image, ray_idxs, feature_table, cameras, vox,
+                                  rvc, Sr, order)
         assert order is None or len(order) == n
         self._check(self.lib.rn_scene_prepare_all(
             self._h, int(n_images), n, int(rows_per_image), _ptr(ray_idxs),
@@ -1264,16 +1269,11 @@ class HipContext(object):
         stats [3, rows] / stats_image [3, n_images, R]: the depth sweeps also write confidence,
         expected depth and depth std (rn_scene_depth_stats) next to the depths -- in row order,
         or, with depth_image, in pixel order."""
-        n, rows = len(ray_idxs), int(n_images) * int(rows_per_image)
-        f32, i32, ra = torch.float32, torch.int32, self._row_align
-        assert rows_per_image % 256 == 0 and n <= rows_per_image
-        _chk(feature_table, torch.int64, n_images * self.N, "feature_table", align=8)
-        assert tuple(feature_table.shape) == (n_images, self.N)
-        _chk(cameras, f32, n_images * (12 * self.N + 16), "cameras")
-        assert tuple(cameras.shape) == (n_images, 12 * self.N + 16)
-        _chk(ray_idxs, i32, n, "ray_idxs"); _chk(order, i32, n, "order", optional=True)
-        _chk(vox, i32, rows * self.M, "vox", align=ra); _chk(rvc, i32, rows, "rvc")
-        _chk(Sr, f32, rows * self.M, "Sr", align=ra); _chk(msgs, f32, rows * self.M, "msgs", align=ra)
+        assert rows_per_image % 256 == 0 and len(ray_idxs) <= rows_per_image
+        n, rows = self._chk_scene(n_images, rows_per_image, ray_idxs, feature_table, cameras, vox,
+                                  rvc, Sr, order)
+        f32 = torch.float32
+        _chk(msgs, f32, rows * self.M, "msgs", align=self._row_align)
         _chk(depth, f32, rows, "depth")
         G = self.acc_size()
         _chk(acc0, f32, G, "acc[0]", align=16); _chk(acc1, f32, G, "acc[1]", align=16)
@@ -1345,23 +1345,29 @@ class HipContext(object):
             _chk(part, part_dtype, self.acc_size(), "partial accumulator", align=16)
         return n
 
+    def _bp_sweep(self, entry, part_dtype, Sr, vox, rvc, acc_in, msgs, acc_part, first_sweep,
+                  patch_rows, uniform_acc):
+        """rn_scene_bp_sweep or its fixed-point twin: they differ in the partial sums' type."""
+        n = self._chk_rows(Sr, vox, rvc, msgs, acc_in, acc_part, part_dtype)
+        # a work list bound for another tensor must not meet a launch whose buffer happens to sit
+        # at the address (and have the row count) the list was built for: unbind unless `vox` IS
+        # the tensor it describes
+        items = self._scatter_items
+        if items is not None and items[1] is not vox:
+            self.bind_scatter_items(None)
+        self._check(entry(self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc), _ptr(acc_in), _ptr(msgs),
+                          _ptr(acc_part), (1 if first_sweep else 0) | (2 if uniform_acc else 0),
+                          1 if patch_rows else 0, _stream()))
+
     def scene_bp_sweep(self, Sr, vox, rvc, acc_in, msgs, acc_part, first_sweep=False,
                        patch_rows=False, uniform_acc=False):
-        n = self._chk_rows(Sr, vox, rvc, msgs, acc_in, acc_part)
-        self._drop_foreign_items(vox)
-        self._check(self.lib.rn_scene_bp_sweep(self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc),
-                                               _ptr(acc_in), _ptr(msgs), _ptr(acc_part),
-                                               (1 if first_sweep else 0) | (2 if uniform_acc else 0),
-                                               1 if patch_rows else 0, _stream()))
+        self._bp_sweep(self.lib.rn_scene_bp_sweep, torch.float32, Sr, vox, rvc, acc_in, msgs,
+                       acc_part, first_sweep, patch_rows, uniform_acc)
 
     def scene_bp_sweep_fixed(self, Sr, vox, rvc, acc_in, msgs, acc_part_fixed, first_sweep=False,
                              patch_rows=False, uniform_acc=False):
-        n = self._chk_rows(Sr, vox, rvc, msgs, acc_in, acc_part_fixed, torch.int64)
-        self._drop_foreign_items(vox)
-        self._check(self.lib.rn_scene_bp_sweep_fixed(
-            self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc), _ptr(acc_in), _ptr(msgs),
-            _ptr(acc_part_fixed), (1 if first_sweep else 0) | (2 if uniform_acc else 0),
-            1 if patch_rows else 0, _stream()))
+        self._bp_sweep(self.lib.rn_scene_bp_sweep_fixed, torch.int64, Sr, vox, rvc, acc_in, msgs,
+                       acc_part_fixed, first_sweep, patch_rows, uniform_acc)
 
     def acc_combine_fixed(self, acc_part_fixed, prior, acc_out):
         _chk(acc_part_fixed, torch.int64, acc_out.numel(), "partial accumulator", align=16)
@@ -1397,9 +1403,7 @@ class HipContext(object):
         n = self._chk_rows(Sr, vox, rvc, msgs, acc)
         _chk(S_new, torch.float32, n * self.M, "S_new", optional=True)
         _chk(depth_map, torch.float32, n, "depth_map", optional=True)
-        groups = (n + rays_per_center - 1) // rays_per_center if rays_per_center > 0 else 1
-        _chk(center, torch.float32, 4 * groups if rays_per_center > 0 else 3, "center",
-             optional=depth_map is None, align=4)
+        _chk_centers(center, n, rays_per_center, optional=depth_map is None)
         self._check(self.lib.rn_scene_depth(self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc),
                                             _ptr(acc), _ptr(msgs), _ptr(center),
                                             int(rays_per_center), _ptr(S_new), _ptr(depth_map),
@@ -1419,8 +1423,7 @@ class HipContext(object):
                 stats_offset + n > stats.shape[1]:
             raise ValueError("stats: expected shape (3, >= %d), got %s"
                              % (stats_offset + n, tuple(stats.shape)))
-        groups = (n + rays_per_center - 1) // rays_per_center if rays_per_center > 0 else 1
-        _chk(center, torch.float32, 4 * groups if rays_per_center > 0 else 3, "center", align=4)
+        _chk_centers(center, n, rays_per_center)
         self._check(self.lib.rn_scene_depth_stats(self._h, n, _ptr(Sr), _ptr(vox), _ptr(rvc),
                                                   _ptr(acc), _ptr(msgs), _ptr(center),
                                                   int(rays_per_center), _ptr(S_new),

@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+import abi_header
 from conftest import REPO
 
 
@@ -30,6 +31,68 @@ def test_library_builds_and_exports_header_symbols():
     lib.rn_version.restype = ctypes.c_char_p
     version = lib.rn_version().decode()
     assert version.startswith("raynet_hip") and version.endswith("knobs: | extra:"), version
+
+
+@pytest.mark.parametrize("name", sorted(abi_header.prototypes()))
+def test_every_entry_is_bound_as_the_header_declares_it(name):
+    """Arity, every argument type and the return type: in the table, and on the function object
+    of the loaded library."""
+    from raynet_amd import _lib
+    returns, declared = abi_header.prototype(name)
+    assert name in _lib.SIGNATURES, "%s has no entry in _lib.SIGNATURES" % name
+    sig = _lib.SIGNATURES[name]
+    assert len(sig) == len(declared), (name, len(sig), declared)
+    for k, (arg, ctype) in enumerate(zip(declared, sig)):
+        assert ctype is abi_header.argtype_of(arg, ctype), (name, k, arg, ctype)
+    restype = abi_header.restype_of(returns)
+    assert _lib.RETURNS.get(name, ctypes.c_int) is restype, (name, returns)
+    assert (name in _lib.RETURNS) == (returns != "int"), (name, returns)
+    _lib.build()
+    fn = getattr(_lib.load(), name)
+    assert list(fn.argtypes) == sig and fn.restype is restype, (name, fn.argtypes, fn.restype)
+
+
+def test_the_header_parser_refuses_what_it_does_not_know():
+    for arg in ("size_t n", "rn_config cfg", "rn_ctx ctx", "void stream", "int32_t", "float (*f)(int)",
+                "rn_options **out"):
+        with pytest.raises(ValueError):
+            abi_header.argtype_of(arg)
+    with pytest.raises(ValueError):
+        abi_header.restype_of("float")
+    assert abi_header.argtype_of("const double cell[3]") is ctypes.c_void_p
+    assert abi_header.argtype_of("uint32_t *views", ctypes.POINTER(ctypes.c_uint32)) is \
+        ctypes.POINTER(ctypes.c_uint32)
+    assert abi_header.argtype_of("uint32_t *views", ctypes.POINTER(ctypes.c_int32)) is ctypes.c_void_p
+    assert abi_header.argtype_of("int64_t *counts", ctypes.POINTER(ctypes.c_int64)) is ctypes.c_void_p
+
+
+def test_the_sources_are_the_files_of_csrc_and_the_header():
+    from raynet_amd import _lib
+    srcs = _lib.sources()
+    assert srcs[0] == os.path.join(_lib.CSRC, "raynet_hip.hip") and srcs[-1] == _lib.HEADER
+    found = sorted(os.path.join(_lib.CSRC, f) for f in os.listdir(_lib.CSRC)
+                   if f.endswith((".hip", ".inl", ".h")))
+    assert sorted(srcs[:-1]) == found and len(set(srcs)) == len(srcs) >= 39
+    assert srcs[1:-1] == sorted(srcs[1:-1])
+    assert not any(s.endswith(".so") for s in srcs)
+
+
+def test_build_is_stale_when_any_one_source_is_newer(monkeypatch, tmp_path):
+    """No compile: the compiler call is caught, and the times are a table."""
+    from raynet_amd import _lib
+    monkeypatch.delenv("RAYNET_HIPCC_EXTRA", raising=False)
+    target = str(tmp_path / "libvariant.so")
+    open(target, "w").close()
+    calls = []
+    monkeypatch.setattr(_lib.subprocess, "check_call", lambda cmd, cwd=None: calls.append(cmd))
+    for newer in [None] + _lib.sources():
+        monkeypatch.setattr(_lib.os.path, "getmtime", lambda p: 2.0 if p == newer else 1.0)
+        del calls[:]
+        assert _lib.build(out=target) == target
+        assert len(calls) == (0 if newer is None else 1), newer
+    # the compile line: the translation unit alone, the flags, the target
+    assert calls[0] == [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + _lib.HIPCC_FLAGS + \
+        [_lib.sources()[0], "-o", target]
 
 
 def test_no_timing_only_branches_in_the_product_sources():

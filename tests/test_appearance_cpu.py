@@ -10,20 +10,13 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import appearance_truth as at
 import isosurface_truth as it
 from conftest import REPO
 from host_program import run_host_program
 
 F = np.float32
-
-
-def _prototype(name):
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-    return m.group(1), [" ".join(a.split()) for a in m.group(2).split(",")]
 
 
 @pytest.mark.parametrize("name,params", [
@@ -37,21 +30,14 @@ def _prototype(name):
       "float *colors", "float *weight", "uint32_t *views", "void *stream"]),
 ])
 def test_entries_are_declared_and_bound_with_matching_types(name, params):
+    """(The types of every entry, these two included: tests/test_abi.py.)"""
     from raynet_amd import _lib
-    returns, declared = _prototype(name)
-    assert returns == "int" and declared == params
-    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(declared)
-    for arg, ctype in zip(declared, _lib.SIGNATURES[name]):
-        want = (ctypes.c_void_p if "*" in arg else
-                ctypes.c_int32 if arg.startswith("int32_t") else
-                ctypes.c_int64 if arg.startswith("int64_t") else
-                ctypes.c_double if arg.startswith("double ") else None)
-        assert ctype is want, (name, arg, ctype)
+    assert abi_header.prototype(name) == ("int", params)
+    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(params)
     assert hasattr(ctypes.CDLL(_lib.build()), name)
 
 
 def test_the_kernel_file_is_plain_hip_and_listed():
-    import inspect
     from raynet_amd import _lib
     csrc = os.path.join(REPO, "raynet_amd", "csrc")
     src = open(os.path.join(csrc, "raynet_appearance.inl")).read()
@@ -76,9 +62,8 @@ def test_the_kernel_file_is_plain_hip_and_listed():
     # one instance per channel count
     for c in "1234":
         assert "k_project_colors<%s>" % c in src
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_appearance.inl"' in build and '"raynet_appearance_args.h"' in build
-    assert '"raynet_views_args.h"' in build
+    for f in ("raynet_appearance.inl", "raynet_appearance_args.h", "raynet_views_args.h"):
+        assert os.path.join(csrc, f) in _lib.sources(), f
 
 
 def test_launcher_checks_under_sanitizers(tmp_path):

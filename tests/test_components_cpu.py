@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import components_truth as ct
+import abi_header
 from conftest import REPO
 from host_program import run_host_program
 
@@ -35,7 +36,6 @@ def test_the_launcher_and_the_kernels_use_the_header():
     """raynet_components.inl decides on the header's verdict, unites and finds with its templates,
     and writes the parent array in k_cc_hook only through the policy's compare-and-swap; the
     policy is relaxed and at agent scope; the header holds no HIP."""
-    import inspect
     from raynet_amd import _lib
     src = open(os.path.join(CSRC, "raynet_components.inl")).read()
     code = re.sub(r"//.*", "", src)
@@ -80,26 +80,16 @@ def test_the_launcher_and_the_kernels_use_the_header():
         assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", open(os.path.join(CSRC, f)).read(),
                              re.M), f
     assert '#include "raynet_components.inl"' in open(os.path.join(CSRC, "raynet_hip.hip")).read()
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_components.inl"' in build and '"raynet_components_args.h"' in build
+    for f in ("raynet_components.inl", "raynet_components_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_entry_is_declared_and_bound_with_matching_types():
+    """(The types of every entry, this one included: tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\b(int|int64_t)\s+rn_mesh_components\s*\(([^)]*)\)\s*;", text)
-    assert m is not None, "rn_mesh_components is not declared in include/raynet_hip.h"
-    declared = [" ".join(a.split()) for a in m.group(2).split(",")]
-    assert m.group(1) == "int" and declared == [
+    assert abi_header.prototype("rn_mesh_components") == ("int", [
         "rn_ctx *ctx", "int64_t nv", "int64_t nf", "const int32_t *faces", "int32_t *labels",
-        "int32_t *vertex_counts", "int32_t *face_counts", "int32_t *status", "void *stream"]
-    sig = _lib.SIGNATURES["rn_mesh_components"]
-    assert len(sig) == len(declared)
-    for arg, ctype in zip(declared, sig):
-        want = (ctypes.c_void_p if "*" in arg else
-                ctypes.c_int64 if arg.startswith("int64_t") else None)
-        assert ctype is want, (arg, ctype)
+        "int32_t *vertex_counts", "int32_t *face_counts", "int32_t *status", "void *stream"])
     assert hasattr(ctypes.CDLL(_lib.build()), "rn_mesh_components")
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fusion_truth as ft
+import abi_header
 from conftest import REPO
 from host_program import run_host_program
 
@@ -25,7 +26,6 @@ def test_launcher_checks_under_sanitizers(tmp_path):
 def test_the_launcher_and_the_kernel_use_these_checks():
     """raynet_fusion.inl decides on the header's verdict, finds its voxel and addresses the maps
     with its functions; the file is plain HIP without LDS, atomics or a square root."""
-    import inspect
     from raynet_amd import _lib
     src = open(os.path.join(CSRC, "raynet_fusion.inl")).read()
     code = re.sub(r"//.*", "", src)
@@ -49,28 +49,17 @@ def test_the_launcher_and_the_kernel_use_these_checks():
     header = open(os.path.join(CSRC, "raynet_fusion_args.h")).read()
     assert "hip" not in re.sub(r"//.*", "", header).lower()
     assert '#include "raynet_fusion.inl"' in open(os.path.join(CSRC, "raynet_hip.hip")).read()
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_fusion.inl"' in build and '"raynet_fusion_args.h"' in build
+    for f in ("raynet_fusion.inl", "raynet_fusion_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_entry_is_declared_and_bound_with_matching_types():
+    """(The types of every entry, this one included: tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\b(int|int64_t)\s+rn_tsdf_integrate\s*\(([^)]*)\)\s*;", text)
-    assert m is not None, "rn_tsdf_integrate is not declared in include/raynet_hip.h"
-    declared = [" ".join(a.split()) for a in m.group(2).split(",")]
-    assert m.group(1) == "int" and declared == [
+    assert abi_header.prototype("rn_tsdf_integrate") == ("int", [
         "rn_ctx *ctx", "int32_t V", "const double *cameras", "int32_t H", "int32_t W",
         "const float *depths", "const float *weights", "double trunc", "double border",
-        "float *tsdf", "float *weight", "void *stream"]
-    sig = _lib.SIGNATURES["rn_tsdf_integrate"]
-    assert len(sig) == len(declared)
-    for arg, ctype in zip(declared, sig):
-        want = (ctypes.c_void_p if "*" in arg else
-                ctypes.c_int32 if arg.startswith("int32_t") else
-                ctypes.c_double if arg.startswith("double ") else None)
-        assert ctype is want, (arg, ctype)
+        "float *tsdf", "float *weight", "void *stream"])
     assert hasattr(ctypes.CDLL(_lib.build()), "rn_tsdf_integrate")
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import holes_truth as ht
+import abi_header
 from conftest import REPO
 from host_program import run_host_program
 
@@ -88,14 +89,14 @@ def test_the_launcher_and_the_kernels_use_the_header():
     assert unit.count('#include "raynet_holes.inl"') == 1
     assert unit.index('"raynet_scan.inl"') < unit.index('"raynet_holes.inl"')
     assert unit.index('"raynet_components.inl"') < unit.index('"raynet_holes.inl"')
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_holes.inl"' in build and '"raynet_holes_args.h"' in build
+    for f in ("raynet_holes.inl", "raynet_holes_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_entries_are_declared_and_bound_with_matching_types():
+    """(The types of every entry, these included, and the restype of the size entry:
+    tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     want = {
         "rn_mesh_fill_holes_workspace_bytes": ("int64_t", ["int64_t nv", "int64_t nf"]),
         "rn_mesh_fill_holes": ("int", [
@@ -104,19 +105,9 @@ def test_the_entries_are_declared_and_bound_with_matching_types():
             "int32_t max_edges", "float *new_vertices", "int32_t *new_faces", "int32_t *source",
             "int64_t *counts", "void *workspace", "void *stream"])}
     lib = ctypes.CDLL(_lib.build())
-    for name, (returns, arguments) in want.items():
-        m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-        declared = [" ".join(a.split()) for a in m.group(2).split(",")]
-        assert m.group(1) == returns and declared == arguments
-        sig = _lib.SIGNATURES[name]
-        assert len(sig) == len(declared)
-        for arg, ctype in zip(declared, sig):
-            expect = (ctypes.c_void_p if "*" in arg else
-                      ctypes.c_int64 if arg.startswith("int64_t") else ctypes.c_int32)
-            assert ctype is expect, (arg, ctype)
+    for name, prototype in want.items():
+        assert abi_header.prototype(name) == prototype
         assert hasattr(lib, name)
-    assert "lib.rn_mesh_fill_holes_workspace_bytes.restype = ctypes.c_int64" in inspect.getsource(_lib.load)
     # the size entry needs no context and no GPU: the header's arithmetic
     fn = lib.rn_mesh_fill_holes_workspace_bytes
     fn.restype, fn.argtypes = ctypes.c_int64, _lib.SIGNATURES["rn_mesh_fill_holes_workspace_bytes"]

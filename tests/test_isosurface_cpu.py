@@ -11,19 +11,12 @@ import sys
 import numpy as np
 import pytest
 
+import abi_header
 import isosurface_truth as it
 from conftest import REPO
 from host_program import run_host_program
 
 F = np.float32
-
-
-def _prototype(name):
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-    return m.group(1), [" ".join(a.split()) for a in m.group(2).split(",")]
 
 
 @pytest.mark.parametrize("name,returns,params", [
@@ -37,19 +30,11 @@ def _prototype(name):
       "int32_t *faces_out", "void *stream"]),
 ])
 def test_entries_are_declared_and_bound_with_matching_arity(name, returns, params):
+    """(The types of every entry, these three included: tests/test_abi.py.)"""
     from raynet_amd import _lib
-    declared_returns, declared = _prototype(name)
-    assert declared_returns == returns and declared == params
-    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(declared)
-    # scalars where the header has scalars, pointers elsewhere
-    for arg, ctype in zip(declared, _lib.SIGNATURES[name]):
-        want = (ctypes.c_void_p if "*" in arg else
-                ctypes.c_int32 if arg.startswith("int32_t") else
-                ctypes.c_int64 if arg.startswith("int64_t") else
-                ctypes.c_float if arg.startswith("float ") else None)
-        assert ctype is want, (name, arg, ctype)
-    path = _lib.build()
-    assert hasattr(ctypes.CDLL(path), name)
+    assert abi_header.prototype(name) == (returns, params)
+    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(params)
+    assert hasattr(ctypes.CDLL(_lib.build()), name)
 
 
 def test_the_kernel_file_is_plain_hip_and_listed():
@@ -66,9 +51,8 @@ def test_the_kernel_file_is_plain_hip_and_listed():
     assert "rn_iso::count_args(" in src and "rn_iso::emit_args(" in src
     assert src.count("rn_iso::row_in(") == 2 and src.count("rn_iso::row_index(") == 4
     # a change of either file rebuilds the library
-    import inspect
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_isosurface.inl"' in build and '"raynet_isosurface_args.h"' in build
+    for f in ("raynet_isosurface.inl", "raynet_isosurface_args.h"):
+        assert os.path.join(csrc, f) in _lib.sources(), f
 
 
 def test_the_table_in_the_kernel_file_is_the_derived_one():

@@ -4,7 +4,6 @@ undefined-behaviour sanitizers -- nothing sanitised is loaded into this interpre
 in the header, in the ctypes table and in the built library, metrics.photometric_error on
 hand-made arrays, MeshRender's images on hand-made planes, and what the command line refuses."""
 import ctypes
-import inspect
 import os
 import re
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import render_truth as rd
+import abi_header
 from conftest import REPO
 from host_program import run_host_program
 
@@ -24,27 +24,17 @@ def test_every_verdict_and_both_lane_mappings_under_sanitizers(tmp_path):
 
 
 def test_the_entry_is_declared_bound_and_built_with_matching_types():
+    """(The types of every entry, this one included, in the table and on the loaded function:
+    tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     arguments = ["rn_ctx *ctx", "const float *nodes", "const float *leaves", "int64_t nv",
                  "const float *vertices", "int64_t nf", "const int32_t *faces", "const float *colors",
                  "int32_t C", "const float *normals", "int32_t V", "const float *cameras",
                  "int32_t H", "int32_t W", "int32_t *face", "float *depth", "float *bary",
                  "float *color", "float *normal", "void *stream"]
-    m = re.search(r"\bint\s+rn_mesh_render\s*\(([^)]*)\)\s*;", text)
-    assert m is not None, "rn_mesh_render is not declared in include/raynet_hip.h"
-    declared = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert declared == arguments
-    sig = _lib.SIGNATURES["rn_mesh_render"]
-    assert len(sig) == len(declared)
-    for arg, ctype in zip(declared, sig):
-        expect = (ctypes.c_void_p if "*" in arg else
-                  ctypes.c_int64 if arg.startswith("int64_t") else ctypes.c_int32)
-        assert ctype is expect, (arg, ctype)
+    assert abi_header.prototype("rn_mesh_render") == ("int", arguments)
     assert hasattr(ctypes.CDLL(_lib.build()), "rn_mesh_render")
     lib = _lib.load()
-    assert lib.rn_mesh_render.argtypes == sig and lib.rn_mesh_render.restype is ctypes.c_int
     # without a context the entry refuses before it touches anything: no GPU needed
     null = ctypes.c_void_p(0)
     assert lib.rn_mesh_render(null, null, null, 3, null, 1, null, null, 0, null, 1, null, 4, 4,
@@ -53,8 +43,8 @@ def test_the_entry_is_declared_bound_and_built_with_matching_types():
     unit = open(os.path.join(CSRC, "raynet_hip.hip")).read()
     assert unit.count('#include "raynet_render.inl"') == 1
     assert unit.index('"raynet_mesh.inl"') < unit.index('"raynet_render.inl"')
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_render.inl"' in build and '"raynet_render_args.h"' in build
+    for f in ("raynet_render.inl", "raynet_render_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_kernel_uses_the_header_and_leaves_the_traversal_alone():

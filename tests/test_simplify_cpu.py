@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import components_truth as ct
 import simplify_truth as sp
 import smooth_truth as st
@@ -32,7 +33,6 @@ def test_the_launcher_and_the_kernels_use_the_header():
     and the atomics policy (the binning also the integer sums within a wavefront): no subscript,
     no arithmetic on positions, no LDS, no floating-point atomic; the scan is the library's one;
     the header holds no HIP and no conditional."""
-    import inspect
     from raynet_amd import _lib
     src = open(os.path.join(CSRC, "raynet_simplify.inl")).read()
     code = re.sub(r"//.*", "", src)
@@ -73,14 +73,14 @@ def test_the_launcher_and_the_kernels_use_the_header():
                              re.M), f
     unit = open(os.path.join(CSRC, "raynet_hip.hip")).read()
     assert unit.count('#include "raynet_simplify.inl"') == 1
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_simplify.inl"' in build and '"raynet_simplify_args.h"' in build
+    for f in ("raynet_simplify.inl", "raynet_simplify_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_entries_are_declared_and_bound_with_matching_types():
+    """(The types of every entry, these included, and the restype of the size entry:
+    tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     want = {
         "rn_mesh_simplify_workspace_bytes": ("int64_t", ["int64_t nv", "int64_t nf",
                                                          "const int32_t dims[3]"]),
@@ -91,20 +91,9 @@ def test_the_entries_are_declared_and_bound_with_matching_types():
             "int32_t *source", "int32_t *cluster", "int64_t *counts", "void *workspace",
             "void *stream"])}
     lib = ctypes.CDLL(_lib.build())
-    for name, (returns, arguments) in want.items():
-        m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-        declared = [" ".join(a.split()) for a in m.group(2).split(",")]
-        assert m.group(1) == returns and declared == arguments
-        sig = _lib.SIGNATURES[name]
-        assert len(sig) == len(declared)
-        for arg, ctype in zip(declared, sig):
-            expect = (ctypes.c_void_p if "*" in arg or "[" in arg else
-                      ctypes.c_int64 if arg.startswith("int64_t") else None)
-            assert ctype is expect, (arg, ctype)
+    for name, prototype in want.items():
+        assert abi_header.prototype(name) == prototype
         assert hasattr(lib, name)
-    import inspect
-    assert "lib.rn_mesh_simplify_workspace_bytes.restype = ctypes.c_int64" in inspect.getsource(_lib.load)
     # the size entry needs no context and no GPU: the header's arithmetic
     fn = lib.rn_mesh_simplify_workspace_bytes
     fn.restype, fn.argtypes = ctypes.c_int64, _lib.SIGNATURES["rn_mesh_simplify_workspace_bytes"]

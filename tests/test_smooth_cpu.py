@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import components_truth as ct
 import smooth_truth as st
 from conftest import REPO
@@ -33,7 +34,6 @@ def test_the_launcher_and_the_kernels_use_the_header():
     """raynet_smooth.inl decides on the header's verdict, lays out the workspace and walks the
     steps with its functions; the kernels call ring_entry / step_vertex and add the index of the
     thread: no subscript, no arithmetic on positions, no atomics, no LDS; the header holds no HIP."""
-    import inspect
     from raynet_amd import _lib
     src = open(os.path.join(CSRC, "raynet_smooth.inl")).read()
     code = re.sub(r"//.*", "", src)
@@ -60,14 +60,14 @@ def test_the_launcher_and_the_kernels_use_the_header():
         assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", open(os.path.join(CSRC, f)).read(),
                              re.M), f
     assert '#include "raynet_smooth.inl"' in open(os.path.join(CSRC, "raynet_hip.hip")).read()
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_smooth.inl"' in build and '"raynet_smooth_args.h"' in build
+    for f in ("raynet_smooth.inl", "raynet_smooth_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_entries_are_declared_and_bound_with_matching_types():
+    """(The types of every entry, these included, and the restype of the size entry:
+    tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     want = {
         "rn_mesh_smooth_workspace_bytes": ("int64_t", ["rn_ctx *ctx", "int64_t nv", "int64_t nf"]),
         "rn_mesh_smooth": ("int", [
@@ -76,22 +76,9 @@ def test_the_entries_are_declared_and_bound_with_matching_types():
             "const uint8_t *fixed", "int32_t iterations", "double lambda", "double mu",
             "double max_move", "void *workspace", "float *vertices_out", "void *stream"])}
     lib = ctypes.CDLL(_lib.build())
-    for name, (returns, arguments) in want.items():
-        m = re.search(r"\b(int|int64_t)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-        declared = [" ".join(a.split()) for a in m.group(2).split(",")]
-        assert m.group(1) == returns and declared == arguments
-        sig = _lib.SIGNATURES[name]
-        assert len(sig) == len(declared)
-        for arg, ctype in zip(declared, sig):
-            expect = (ctypes.c_void_p if "*" in arg else
-                      ctypes.c_int64 if arg.startswith("int64_t") else
-                      ctypes.c_int32 if arg.startswith("int32_t") else
-                      ctypes.c_double if arg.startswith("double") else None)
-            assert ctype is expect, (arg, ctype)
+    for name, prototype in want.items():
+        assert abi_header.prototype(name) == prototype
         assert hasattr(lib, name)
-    import inspect
-    assert "lib.rn_mesh_smooth_workspace_bytes.restype = ctypes.c_int64" in inspect.getsource(_lib.load)
 
 
 # ------------------------------------------------------------- the plumbing, on the truth's steps

@@ -4,13 +4,13 @@ undefined-behaviour sanitizers -- nothing sanitised is loaded into this interpre
 entries in the header, in the ctypes table and in the built library, what the new kernel file may
 contain, what the three command lines refuse, and the OBJ triple of a hand-made mesh read back."""
 import ctypes
-import inspect
 import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_header
 from conftest import REPO
 from host_program import run_host_program
 
@@ -33,30 +33,20 @@ def test_every_verdict_the_layout_and_both_lane_mappings_under_sanitizers(tmp_pa
 
 @pytest.mark.parametrize("name,arguments", [("rn_texture_bake", BAKE), ("rn_texture_sample", SAMPLE)])
 def test_the_entries_are_declared_bound_and_built_with_matching_types(name, arguments):
+    """(The types of every entry, these two included, in the table and on the loaded function:
+    tests/test_abi.py.)"""
     from raynet_amd import _lib
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-    declared = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert declared == arguments
-    sig = _lib.SIGNATURES[name]
-    assert len(sig) == len(declared)
-    for arg, ctype in zip(declared, sig):
-        expect = (ctypes.c_void_p if "*" in arg else ctypes.c_int64 if arg.startswith("int64_t")
-                  else ctypes.c_double if arg.startswith("double") else ctypes.c_int32)
-        assert ctype is expect, (arg, ctype)
+    assert abi_header.prototype(name) == ("int", arguments)
     assert hasattr(ctypes.CDLL(_lib.build()), name)
     fn = getattr(_lib.load(), name)
-    assert fn.argtypes == sig and fn.restype is ctypes.c_int
     # without a context the entry refuses before it touches anything: no GPU needed
     null = ctypes.c_void_p(0)
     values = [null if "*" in a else (0.0 if a.startswith("double") else 1) for a in arguments]
     assert fn(*values) == -1
     unit = open(os.path.join(CSRC, "raynet_hip.hip")).read()
     assert unit.count('#include "raynet_texture.inl"') == 1
-    build = inspect.getsource(_lib.build)
-    assert '"raynet_texture.inl"' in build and '"raynet_texture_args.h"' in build
+    for f in ("raynet_texture.inl", "raynet_texture_args.h"):
+        assert os.path.join(CSRC, f) in _lib.sources(), f
 
 
 def test_the_kernels_are_plain_and_use_the_header():

@@ -2,7 +2,6 @@
 raynet_amd/csrc/raynet_views_args.h as a stand-alone program under the address and
 undefined-behaviour sanitizers -- nothing sanitised is loaded into this interpreter -- and where
 the header may be named."""
-import inspect
 import os
 import re
 
@@ -23,7 +22,7 @@ def test_the_header_is_plain_guards_its_loads_and_is_stated_once():
     assert "#pragma once" in header and "namespace rn_view" in header
     assert "hip" not in code.lower() and "__device__" not in code and "sqrt" not in code
     assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", header, re.M)
-    assert '"raynet_views_args.h"' in inspect.getsource(_lib.build)
+    assert os.path.join(CSRC, "raynet_views_args.h") in _lib.sources()
     # every image and depth load goes through image_index / map_index with pixel_in-guarded
     # coordinates
     loads = re.findall(r"a\.(images|depths)\[(\w+)\(", code)

@@ -1,21 +1,12 @@
 """The occupancy volume's host side (no GPU): the two entries in the header and the ctypes table,
 the command lines' flags, OccupancyVolume's file and its voxel cloud."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
-
-
-def _prototype(name):
-    text = open(os.path.join(REPO, "include", "raynet_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m is not None, "%s is not declared in include/raynet_hip.h" % name
-    return [a.strip() for a in m.group(1).split(",")]
+import abi_header
 
 
 @pytest.mark.parametrize("name,params", [
@@ -27,19 +18,12 @@ def _prototype(name):
                           "void *stream"]),
 ])
 def test_entries_are_declared_and_bound_with_matching_arity(name, params):
+    """(The types of every entry, these two included: tests/test_abi.py.)"""
     import ctypes
     from raynet_amd import _lib
-    declared = [" ".join(a.split()) for a in _prototype(name)]
-    assert declared == params
-    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(declared)
-    # scalars where the header has scalars, pointers elsewhere
-    for arg, ctype in zip(declared, _lib.SIGNATURES[name]):
-        want = (ctypes.c_int32 if arg.startswith("int32_t") else
-                ctypes.c_int64 if arg.startswith("int64_t") else
-                ctypes.c_float if arg.startswith("float ") and "*" not in arg else ctypes.c_void_p)
-        assert ctype is want, (name, arg, ctype)
-    path = _lib.build()
-    assert hasattr(ctypes.CDLL(path), name)
+    assert abi_header.prototype(name) == ("int", params)
+    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == len(params)
+    assert hasattr(ctypes.CDLL(_lib.build()), name)
 
 
 def test_forward_pass_parser_knows_save_occupancy():
