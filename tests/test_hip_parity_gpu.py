@@ -90,7 +90,9 @@ def test_sample_points_k8(torch, oracle_mod):
 @pytest.mark.parametrize("generic", [False, True])
 def test_similarities(torch, oracle_mod, case, generic):
     """K7.  The generic sweep walks the dot product in the reference's order (equal to
-    the oracle up to expf); the cooperative F=32 sweep re-associates the 32-term sums."""
+    the oracle up to expf); the cooperative F=32 sweep re-associates the 32-term sums.
+    (Flat features, an absolute bar: the accuracy of the values, per flavour and under features
+    that show a wrong softmax maximum, is tests/test_sweep_launches_gpu.py.)"""
     from raynet_amd.hip_implementations.options import PathOptions
     c = CU[case]
     o, feats, _ = make_case(oracle_mod, c)

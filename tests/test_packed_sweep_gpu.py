@@ -4,7 +4,11 @@ the one-ray-per-wavefront kernel it replaces there (rn_options.sweep_rays_per_wa
 bits are required, the per-sample instruction sequence is the same) and against the oracle, through
 every entry that sweeps: K7, K9 / K10, K11, the resident prepare (with and without the folded first
 BP iteration) and the whole forward pass.  Odd ray counts (a wavefront's last ray slots empty),
-D not a power of two (rounds of dead samples skipped), 2 ... 9 views."""
+D not a power of two (rounds of dead samples skipped), 2 ... 9 views.
+
+What is held here is SAMENESS (and the oracle at 1e-5 under flat features, which cannot see a wrong
+softmax maximum); the VALUE of every flavour's column per launch, against a float64 truth and
+under features that can, is tests/test_sweep_launches_gpu.py."""
 import numpy as np
 import pytest
 
