@@ -1005,6 +1005,49 @@ int rn_tsdf_integrate(rn_ctx *ctx, int32_t V, const double *cameras, int32_t H, 
                       const float *depths, const float *weights, double trunc, double border,
                       float *tsdf, float *weight, void *stream);
 
+/* ---- what the other views say about a point ----
+ *
+ * rn_points_consistency: every view's verdict on every point in one launch.  All arrays are device
+ * memory.  points [3][n] f64, the coordinates as three rows (the layout rn_depthmap_points writes);
+ * cameras [V][15] f64, a row P [3][4] row-major | centre [3] (as for rn_project_colors); depths
+ * [V][H][W] f32, distances to the camera centre, pixel centres at whole coordinates.
+ * 1 <= V <= 32; exclude: the one view that is skipped (the view the points came from), -1 for
+ * none.  Written: seen, agree, violate [n] u32, bit v for view v, and residual [n] f32 -- all n
+ * entries, always.
+ *
+ * One thread per point p = (x, y, z); the views v in ascending order, v == exclude skipped.  Every
+ * operation is fp64 and rounded on its own, in the order written (the library is built with
+ * -ffp-contract=off); only + - * /, rint, comparisons and conversions occur -- no sqrt -- so a
+ * NumPy restatement gives the same bits (tests/consistency_truth.py):
+ *   projection   exactly as rn_project_colors and rn_tsdf_integrate: X, Y, dd, and
+ *   in view      0 < h_2 < inf,  dd > 0,  border <= X <= (W - 1) - border,
+ *                border <= Y <= (H - 1) - border             (a NaN fails every test)
+ *   measurement  z = depths[v][rint(Y)][rint(X)] (half to even);
+ *                measured = in view and 0 < z < inf
+ *   distance     s = (z z - dd) / (z + z);   t = tol_abs + tol_rel z
+ *   verdict      agrees   = measured and -t <= s <= t
+ *                violates = measured and s > t      (the view sees past the point: the point
+ *                                                    floats in that view's free space)
+ *                a measured view with s < -t only fails to see the point (it is occluded there):
+ *                bit v of seen alone
+ *   masks        bit v of seen / agree / violate is set iff measured / agrees / violates
+ *   sums         where the view agrees: num = num + s;  cnt = cnt + 1
+ *   result       residual = cnt > 0 ? (float)(num / cnt) : 0.0f
+ * A view that is not in view reads pixel (0, 0) of its map, so every load lies inside the arrays
+ * whatever the points and cameras hold.  A NaN or infinite point sets no bit.  The depth is read at
+ * the nearest pixel: a tolerance must exceed the depth step of one pixel of the surfaces it is to
+ * confirm.
+ *
+ * n == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch: n negative
+ * or above 2^38, V outside 1..32, H or W below 1, exclude outside -1..V-1, tol_abs, tol_rel or
+ * border negative or not finite, and with n > 0 a NULL points, cameras, depths, seen, agree,
+ * violate or residual. */
+int rn_points_consistency(rn_ctx *ctx, int64_t n, const double *points, int32_t V,
+                          const double *cameras, int32_t H, int32_t W, const float *depths,
+                          int32_t exclude, double tol_abs, double tol_rel, double border,
+                          uint32_t *seen, uint32_t *agree, uint32_t *violate, float *residual,
+                          void *stream);
+
 /* ---- the connected components of an indexed triangle mesh ----
  *
  * rn_mesh_components: which piece every vertex belongs to, and how large the pieces are.  Two

@@ -1241,6 +1241,9 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // depth maps fused into a truncated signed distance volume
 #include "raynet_fusion.inl"
 
+// what the other views say about a point: seen, agreeing and violated masks
+#include "raynet_consistency.inl"
+
 // the connected components of a surface mesh: a lock-free union-find
 #include "raynet_components.inl"
 

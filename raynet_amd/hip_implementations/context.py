@@ -478,6 +478,40 @@ class HipContext(object):
             float(border), _ptr(tsdf), _ptr(weight), _stream()))
         return tsdf, weight
 
+    # ---- the other views' verdict on points (raynet_amd/consistency.py) -----------------------
+    def points_consistency(self, points, cameras, depths, exclude, tol_abs, tol_rel, border,
+                           seen=None, agree=None, violate=None, residual=None):
+        """rn_points_consistency: points (3, n) f64, cameras (V, 15) f64, depths (V, H, W) f32 of
+        distances to the camera centres, 1 <= V <= 32, exclude: the view that is skipped or -1 ->
+        (seen, agree, violate, residual): three [n] int32 (the bits of the u32 masks, bit v for
+        view v: it measures something at the point's pixel / agrees with the point within
+        tol_abs + tol_rel * depth / sees past the point) and [n] f32, the mean signed distance
+        over the agreeing views, 0 where none agrees."""
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] != 3:
+            raise ValueError("points: expected shape (3, n), got %s"
+                             % (tuple(getattr(points, "shape", ())),))
+        n = int(points.shape[1])
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        V, H, W = _stack(depths, None, "depths")
+        if not 1 <= V <= 32:
+            raise ValueError("depths: 1 to 32 views (a bit of the masks each), got %d" % V)
+        _table(cameras, 15, torch.float64, "cameras", align=8, rows=V)
+        exclude = int(exclude)
+        if not -1 <= exclude < V:
+            raise ValueError("exclude: a view 0..%d or -1, got %d" % (V - 1, exclude))
+        outs = []
+        for t, name, dtype in ((seen, "seen", torch.int32), (agree, "agree", torch.int32),
+                               (violate, "violate", torch.int32),
+                               (residual, "residual", torch.float32)):
+            if t is None:
+                t = torch.empty((n,), dtype=dtype, device=points.device)
+            outs.append(_chk(t, dtype, n, name))
+        self._check(self.lib.rn_points_consistency(
+            self._h, n, _ptr(points), V, _ptr(cameras), H, W, _ptr(depths), exclude,
+            float(tol_abs), float(tol_rel), float(border), _ptr(outs[0]), _ptr(outs[1]),
+            _ptr(outs[2]), _ptr(outs[3]), _stream()))
+        return tuple(outs)
+
     # ---- connected components of a mesh (raynet_amd/components.py) ---------------------------
     def mesh_components(self, faces, n_vertices, labels=None, vertex_counts=None, face_counts=None):
         """rn_mesh_components: faces (nf, 3) i32 of a mesh with `n_vertices` vertices -> (labels,

@@ -132,10 +132,12 @@ class PointcloudFromDepthMaps(Pointcloud):
     """raynet/pointcloud.py:76-160.  depthmaps: .npy file names (as the reference) or arrays.
     confidences (file names or arrays like depthmaps, one per frame: the forward pass's
     `confidence` maps) and min_confidence: pixels whose confidence is below the threshold are
-    dropped with the unwanted ones; the defaults select what the reference selects."""
+    dropped with the unwanted ones; keep_masks (one (H, W) bool array per frame, e.g.
+    consistency.DepthConsistency.keep()): pixels that are False there are dropped too; the
+    defaults select what the reference selects."""
 
     def __init__(self, scene, frame_idxs, depthmaps, borders=40, confidences=None,
-                 min_confidence=0.0):
+                 min_confidence=0.0, keep_masks=None):
         self._scene = scene
         self._frame_idxs = frame_idxs
         self._depthmaps = depthmaps
@@ -147,15 +149,19 @@ class PointcloudFromDepthMaps(Pointcloud):
         if confidences is None and self._min_confidence > 0:
             raise ValueError("min_confidence=%g needs the confidence maps" % self._min_confidence)
         self._confidence_of = dict(zip(frame_idxs, confidences)) if confidences is not None else None
+        if keep_masks is not None and len(keep_masks) != len(frame_idxs):
+            raise ValueError("%d keep masks for %d frames" % (len(keep_masks), len(frame_idxs)))
+        self._keep_of = dict(zip(frame_idxs, keep_masks)) if keep_masks is not None else None
 
     @staticmethod
     def _load(d):
         return np.load(d) if isinstance(d, str) else np.asarray(d)
 
-    def _selected_pixels(self, G, confidence=None):
+    def _selected_pixels(self, G, confidence=None, keep_mask=None):
         """Indices u*H + v of the pixels that survive _remove_unwanted_points
         (pointcloud.py:91-119), in the reference's order -- and, given the frame's confidence
-        map, whose confidence is not below min_confidence."""
+        map, whose confidence is not below min_confidence, and, given the frame's keep mask,
+        which are True there."""
         H, W = G.shape
         b = self._borders
         idxs = torch.arange(H * W, device="cuda").reshape(W, H).t()
@@ -167,6 +173,11 @@ class PointcloudFromDepthMaps(Pointcloud):
             if tuple(C.shape) != (H, W):
                 raise ValueError("confidence map %s for a %s depth map" % (tuple(C.shape), (H, W)))
             keep = keep & ~(C[sl] < self._min_confidence)
+        if keep_mask is not None:
+            K = _dev(np.asarray(keep_mask), torch.bool)
+            if tuple(K.shape) != (H, W):
+                raise ValueError("keep mask %s for a %s depth map" % (tuple(K.shape), (H, W)))
+            keep = keep & K[sl]
         return idxs[sl][keep]
 
     def _all_points(self, frame, depth):
@@ -187,7 +198,8 @@ class PointcloudFromDepthMaps(Pointcloud):
         depth = self._load(predicted_depth)
         sel = self._selected_pixels(
             self._scene.get_depth_map(frame),
-            self._confidence_of[frame] if self._confidence_of is not None else None)
+            self._confidence_of[frame] if self._confidence_of is not None else None,
+            self._keep_of[frame] if self._keep_of is not None else None)
         return self._all_points(frame, depth)[:, sel]
 
     @property
@@ -235,9 +247,14 @@ class PointcloudFromDepthMapsWithConsistency(PointcloudFromDepthMaps):
 
 
 def get_pointcloud(scene, frame_idxs, depthmaps, with_consistency, **kwargs):
-    """raynet/pointcloud.py:248-269; optional kwargs confidences, min_confidence."""
+    """raynet/pointcloud.py:248-269; optional kwargs confidences, min_confidence and, without the
+    reference's consistency check, keep_masks."""
     conf = dict(confidences=kwargs.get("confidences"),
                 min_confidence=kwargs.get("min_confidence", 0.0))
+    if kwargs.get("keep_masks") is not None:
+        if with_consistency:
+            raise ValueError("keep_masks and the reference's consistency check exclude each other")
+        conf["keep_masks"] = kwargs["keep_masks"]
     if with_consistency:
         return PointcloudFromDepthMapsWithConsistency(
             scene, frame_idxs, depthmaps, kwargs["borders"], kwargs["consistency_threshold"],

@@ -16,6 +16,10 @@ clouds are also saved with the colours of the chosen frames' images, as colored_
 (and colored_filtered_predicted_pc_s_%d.ply when filters ran): a frame colours the points it sees,
 with the predicted depth maps as occluders at the tolerance --consistency_threshold, and the frames
 that see a point are blended (Pointcloud.colorize).  At most 32 frames.
+--min_consistent_views K [--max_violations M --consistency_abs X --consistency_rel X] is new as well:
+a pixel becomes a point only if at least K of the other chosen frames agree with its depth and at
+most M see past it (raynet_amd.scripts.consistency_flags; at most 32 frames).
+--with_consistency_check stays the reference's check; the two exclude each other.
 """
 import argparse
 import os
@@ -23,6 +27,7 @@ import sys
 
 import numpy as np
 
+from . import consistency_flags
 from .compute_metrics import frame_idxs_type
 
 
@@ -81,6 +86,7 @@ def build_parser():
     p.add_argument("--color", action="store_true",
                    help="Also write the clouds with the colours of the chosen frames' images "
                         "(colored_*.ply; the depth maps occlude, at --consistency_threshold)")
+    consistency_flags.add_arguments(p)
     return p
 
 
@@ -93,6 +99,10 @@ def main(argv=None):
     if args.color and not args.consistency_threshold >= 0:
         parser.error("--color: --consistency_threshold is the occlusion tolerance and cannot be "
                      "negative")
+    consistency_flags.check(parser, args)
+    if consistency_flags.requested(args) and args.with_consistency_check:
+        parser.error("--min_consistent_views and --with_consistency_check (the reference's check) "
+                     "exclude each other")
     from raynet_amd.common.scene import get_scene
     if args.dataset_type == "dtu":
         scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
@@ -123,6 +133,13 @@ def run(scene, args):
                 "--min_confidence: %d of %d confidence maps are missing (first: %s); write them "
                 "with `forward_pass --depth_statistics`" % (len(missing), len(files), missing[0]))
         confidence = dict(confidences=files, min_confidence=args.min_confidence)
+    if consistency_flags.requested(args):
+        if len(frame_idxs) > consistency_flags.MAX_FRAMES:
+            raise SystemExit("--min_consistent_views: %d frames, at most %d per run; choose them "
+                             "with --frame_idxs" % (len(frame_idxs), consistency_flags.MAX_FRAMES))
+        results = consistency_flags.run(args, scene, frame_idxs, [np.load(d) for d in depthmaps])
+        confidence["keep_masks"] = [c.keep(args.min_consistent_views, args.max_violations)
+                                    for c in results]
     predicted_pointcloud = get_pointcloud(
         scene, frame_idxs, depthmaps, args.with_consistency_check, borders=args.borders,
         consistency_threshold=args.consistency_threshold, n_neighbors=args.n_neighbors,

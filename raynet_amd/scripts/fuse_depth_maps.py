@@ -22,6 +22,11 @@ observation ends.
 --gt                 fuse the scene's ground-truth depth maps instead (PREDICTIONS_DIR is not
                      read): the ground-truth MESH of a scene that ships none, DTU's for instance,
                      for the surface_accuracy / surface_completeness metrics
+--min_consistent_views K [--max_violations M --consistency_abs X --consistency_rel X]
+                     before the fusion, drop every pixel that fewer than K of the other frames
+                     agree with or that more than M frames see past, within X + X * depth
+                     (raynet_amd.scripts.consistency_flags); a line per frame
+                     says how many pixels went, as disagreeing or as violating
 --volume OUT.npz     also save the volume (fusion.TSDFVolume.load reads it back)
 --normals, --color   the mesh file also carries vertex normals / the colours of the frames' images
                      (volume.SurfaceMesh.compute_normals / .colorize; at most 32 frames)
@@ -40,7 +45,7 @@ import sys
 
 import numpy as np
 
-from . import mesh_flags, texture_flags
+from . import consistency_flags, mesh_flags, texture_flags
 from .convert_to_pointcloud import find_format
 
 
@@ -79,6 +84,7 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
     mesh_flags.add_arguments(p)
     texture_flags.add_arguments(p)
+    consistency_flags.add_arguments(p)
     # the dataset and indexing flags of raynet_amd.scripts.render_volume
     p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
     p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
@@ -116,6 +122,9 @@ def main(argv=None):
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
     mesh_flags.check(parser, args)
     texture_flags.check(parser, args)
+    consistency_flags.check(parser, args)
+    if args.gt and consistency_flags.requested(args):
+        parser.error("--min_consistent_views: ground-truth depth maps are not checked")
     from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
 
@@ -134,6 +143,7 @@ def main(argv=None):
         parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
                      "--skip_every" % len(frames))
     texture_flags.check_frames(parser, args, frames)
+    consistency_flags.check_frames(parser, args, frames)
     weights = None
     if args.gt:
         depth_maps = [scene.get_depth_map(i) for i in frames]
@@ -153,6 +163,8 @@ def main(argv=None):
             if args.min_confidence is not None:
                 weights = [np.where(w >= np.float32(args.min_confidence), w, np.float32(0))
                            for w in weights]
+    if consistency_flags.requested(args):
+        depth_maps = consistency_flags.filter_maps(args, scene, frames, depth_maps, args.border)
     volume = fuse_scene(scene, depth_maps, frames, args.grid_shape, trunc=args.truncation,
                         weights=weights, border=args.border)
     if args.volume:
