@@ -22,8 +22,8 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib
-from .appearance import pack_cameras
+from .appearance import _context, pack_cameras
+from .fusion import _stack
 
 MAX_VIEWS = 32
 
@@ -41,14 +41,6 @@ def popcount(mask):
     return np.unpackbits(m.view(np.uint8).reshape(m.shape + (4,)), axis=-1).sum(-1, dtype=np.uint8)
 
 
-def _context():
-    if not torch.cuda.is_available():
-        raise _lib.RaynetHipError(
-            "no GPU visible: raynet_amd checks depth maps on MI355X only (no CPU fallback)")
-    from .hip_implementations import get_context
-    return get_context()
-
-
 def _views(cameras, depth_maps, device):
     """The camera rows and the stacked maps on the device, after the checks that need no GPU
     call."""
@@ -57,13 +49,8 @@ def _views(cameras, depth_maps, device):
         raise ValueError("%d cameras and %d depth maps" % (V, len(depth_maps)))
     if not 1 <= V <= MAX_VIEWS:
         raise ValueError("%d views: 1 to %d per call (a bit of the masks each)" % (V, MAX_VIEWS))
-    maps = [m.detach() if isinstance(m, torch.Tensor) else
-            torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)) for m in depth_maps]
-    depths = torch.stack([m.to(device=device, dtype=torch.float32) for m in maps]).contiguous()
-    if depths.dim() != 3:
-        raise ValueError("depth_maps: (H, W) maps of one shape, got %s" % (tuple(depths.shape[1:]),))
-    rows = torch.from_numpy(pack_cameras(cameras)).to(device)
-    return rows, depths
+    depths = _stack(depth_maps, device, "depth_maps")
+    return torch.from_numpy(pack_cameras(cameras)).to(device), depths
 
 
 def _tolerances(tol_abs, tol_rel, border):
@@ -87,7 +74,7 @@ def check_points(points, cameras, depth_maps, exclude=-1, tol_abs=0.0, tol_rel=0
     p = np.asarray(points.detach().cpu() if isinstance(points, torch.Tensor) else points)
     if p.ndim != 2 or p.shape[1] != 3:
         raise ValueError("points: expected shape (n, 3), got %s" % (p.shape,))
-    ctx = _context()
+    ctx = _context("checks depth maps")
     rows, depths = _views(cameras, depth_maps, ctx.device)
     pts = torch.from_numpy(np.ascontiguousarray(p.T, dtype=np.float64)).to(ctx.device)
     seen, agree, violate, residual = ctx.points_consistency(pts, rows, depths, exclude, tol_abs,
@@ -170,7 +157,7 @@ def check_depth_maps(depth_maps, cameras=None, P_pinvs=None, centers=None, scene
         centers = [c.center for c in cameras]
     if len(P_pinvs) != V or len(centers) != V:
         raise ValueError("%d cameras, %d P_pinvs and %d centers" % (V, len(P_pinvs), len(centers)))
-    ctx = _context()
+    ctx = _context("checks depth maps")
     dev = ctx.device
     rows, depths = _views(cameras, depth_maps, dev)
     _, H, W = (int(s) for s in depths.shape)

@@ -28,16 +28,10 @@ import sys
 
 import numpy as np
 
+from . import scene_flags
+from .scene_flags import frame_idxs_type      # (its home until the scripts shared their flags)
+
 METRICS = ["ppmde", "accuracy", "completeness", "surface_accuracy", "surface_completeness"]
-
-
-def frame_idxs_type(arg):
-    """"a:b:c" -> slice, "1,2,5" -> list, "3" -> [3] (scripts/slicing.py:8-18)."""
-    if ":" in arg:
-        return slice(*[int(x) if x != "" else None for x in arg.split(":")])
-    if "," in arg:
-        return [int(x) for x in arg.split(",")]
-    return [int(arg)]
 
 
 def build_parser():
@@ -47,18 +41,13 @@ def build_parser():
     p.add_argument("metric", nargs="+", choices=METRICS, help="Choose a metric")
     p.add_argument("--output_directory", default="/tmp/",
                    help="The directory to save the predicted point cloud")
-    p.add_argument("--scene_idx", type=int, default=0, help="DTU: the scan number")
-    p.add_argument("--frame_idxs", type=frame_idxs_type, default=":",
-                   help="Choose the frames that correspond to the ordered prediction files")
     p.add_argument("--predicted_files_format", default="depth_%03d.npy",
                    help="The format for the predicted file")
     p.add_argument("--use_pc_from_depthmap", action="store_true",
                    help="Estimate the ground-truth point cloud from the depth images")
-    # scripts/arguments.py:300-330 (dataset)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
+    # scripts/arguments.py:300-330 (dataset).  --scene_idx defaults to 0 here, the reference's
+    # default for this script: the output file names carry it (predicted_pc_s_%d.ply)
+    scene_flags.add_arguments(p, scene_idx=0, frames="frame_idxs")
     # :259-297 (metrics)
     p.add_argument("--borders", default=40, type=int,
                    help="The number of pixels to drop from the borders of the image")
@@ -95,25 +84,17 @@ def build_metric(name, args, filter_factory=None):
 
 def main(argv=None):
     """-> {metric name: its values}, after printing each metric's mean and median."""
-    args = build_parser().parse_args(argv)
-    if isinstance(args.frame_idxs, str):
-        args.frame_idxs = frame_idxs_type(args.frame_idxs)
-    from raynet_amd.common.scene import get_scene
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    return run(scene, args)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    scene_flags.check(parser, args)
+    return run(scene_flags.open_scene(args), args)
 
 
 def run(scene, args, filter_factory=None):
     """The script's body on a scene object (`args`: the parser's namespace).  filter_factory:
     a metrics.FiltersFactory for every cloud metric (None: no filters)."""
     from raynet_amd.pointcloud import get_pointcloud
-    frame_idxs = [int(i) for i in np.arange(scene.n_images)[args.frame_idxs]]
+    frame_idxs = scene_flags.frames(None, args, scene)
     depthmaps = [os.path.join(args.predictions_directory, args.predicted_files_format % (i,))
                  for i in frame_idxs]
     predicted_pointcloud = get_pointcloud(

@@ -27,8 +27,8 @@ import sys
 
 import numpy as np
 
-from . import consistency_flags
-from .compute_metrics import frame_idxs_type
+from . import consistency_flags, scene_flags
+from .scene_flags import find_format, frame_idxs_type     # (their home until the scripts shared them)
 
 
 def build_filter_factory(scene, min_distance, output_directory=None, seed=0):
@@ -44,29 +44,16 @@ def build_filter_factory(scene, min_distance, output_directory=None, seed=0):
     return FiltersFactory(filters)
 
 
-def find_format(input_directory, key, idx):
-    """convert_to_pointcloud.py:30-35: "<key>_%d.npy" if that file of frame idx exists, else
-    "<key>_%03d.npy"."""
-    if os.path.isfile(os.path.join(input_directory, "%s_%d.npy" % (key, idx))):
-        return key + "_%d.npy"
-    return key + "_%03d.npy"
-
-
 def build_parser():
     p = argparse.ArgumentParser(description="Transform the input depth maps to a pointcloud")
     p.add_argument("dataset_directory", help="The dataset to load")
     p.add_argument("predictions_directory", help="The directory containing the model's predictions")
     p.add_argument("output_directory", help="The directory to save the predicted point cloud")
-    p.add_argument("--scene_idx", type=int, default=0, help="DTU: the scan number")
-    p.add_argument("--frame_idxs", type=frame_idxs_type, default=":",
-                   help="Choose the frames that correspond to the ordered prediction files")
     p.add_argument("--pred_suffix", default="depth",
                    help="The suffix for the predicted files (default=depth)")
-    # scripts/arguments.py:300-330 (dataset)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
+    # scripts/arguments.py:300-330 (dataset).  --scene_idx defaults to 0 here, the reference's
+    # default for this script: the output file names carry it (predicted_pc_s_%d.ply)
+    scene_flags.add_arguments(p, scene_idx=0, frames="frame_idxs")
     # :259-297 (metrics)
     p.add_argument("--borders", default=40, type=int,
                    help="The number of pixels to drop from the borders of the image")
@@ -94,8 +81,7 @@ def main(argv=None):
     """-> (predicted cloud, filtered cloud or None), after writing the PLY files."""
     parser = build_parser()
     args = parser.parse_args(argv)
-    if isinstance(args.frame_idxs, str):
-        args.frame_idxs = frame_idxs_type(args.frame_idxs)
+    scene_flags.check(parser, args)
     if args.color and not args.consistency_threshold >= 0:
         parser.error("--color: --consistency_threshold is the occlusion tolerance and cannot be "
                      "negative")
@@ -103,21 +89,13 @@ def main(argv=None):
     if consistency_flags.requested(args) and args.with_consistency_check:
         parser.error("--min_consistent_views and --with_consistency_check (the reference's check) "
                      "exclude each other")
-    from raynet_amd.common.scene import get_scene
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    return run(scene, args)
+    return run(scene_flags.open_scene(args), args)
 
 
 def run(scene, args):
     """The script's body on a scene object (`args`: the parser's namespace)."""
     from raynet_amd.pointcloud import get_pointcloud
-    frame_idxs = [int(i) for i in np.arange(scene.n_images)[args.frame_idxs]]
+    frame_idxs = scene_flags.frames(None, args, scene)
     os.makedirs(args.output_directory, exist_ok=True)
     filter_factory = build_filter_factory(scene, args.min_distance,
                                           output_directory=args.output_directory, seed=args.seed)
@@ -125,6 +103,8 @@ def run(scene, args):
     depthmaps = [os.path.join(args.predictions_directory, fmt % (i,)) for i in frame_idxs]
     confidence = {}
     if getattr(args, "min_confidence", None) is not None:
+        # (not scene_flags.load_maps: no parser in reach here, get_pointcloud takes the paths,
+        # and the message names the flag and the remedy)
         cfmt = find_format(args.predictions_directory, "confidence", frame_idxs[0])
         files = [os.path.join(args.predictions_directory, cfmt % (i,)) for i in frame_idxs]
         missing = [f for f in files if not os.path.isfile(f)]

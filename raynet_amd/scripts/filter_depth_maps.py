@@ -27,12 +27,7 @@ import sys
 
 import numpy as np
 
-from . import consistency_flags
-from .convert_to_pointcloud import find_format
-
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
+from . import consistency_flags, scene_flags
 
 
 def build_parser():
@@ -45,50 +40,24 @@ def build_parser():
     p.add_argument("--border", type=float, default=0.0,
                    help="Pixels to stay away from the edge of the depth maps")
     consistency_flags.add_arguments(p)
-    # the dataset and indexing flags of raynet_amd.scripts.fuse_depth_maps
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
-    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
-    p.add_argument("--start_end", type=_ints, default="0,5")
-    p.add_argument("--skip_every", type=int, default=0)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
+    scene_flags.add_arguments(p)
     return p
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if isinstance(args.start_end, str):
-        args.start_end = _ints(args.start_end)
-    if len(args.start_end) != 2:
-        parser.error("--start_end takes two numbers, START,END")
+    scene_flags.check(parser, args)
     if not 0.0 <= args.border < float("inf"):
         parser.error("--border takes a finite number of pixels, 0 or more")
     if args.min_consistent_views is None:
         args.min_consistent_views = 2               # the check is what this script is for
     consistency_flags.check(parser, args)
-    from raynet_amd.common.scene import get_scene
-
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    start, end = args.start_end
-    frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
-    if not frames:
-        parser.error("--start_end selects no frame of the scene")
+    scene = scene_flags.open_scene(args)
+    frames = scene_flags.frames(parser, args, scene)
     consistency_flags.check_frames(parser, args, frames)
-    fmt = find_format(args.predictions_directory, args.pred_suffix, frames[0])
-    files = [os.path.join(args.predictions_directory, fmt % (i,)) for i in frames]
-    missing = [f for f in files if not os.path.isfile(f)]
-    if missing:
-        parser.error("%d of %d %s maps are missing (first: %s)"
-                     % (len(missing), len(files), args.pred_suffix, missing[0]))
-    depth_maps = [np.asarray(np.load(f), np.float32) for f in files]
+    depth_maps = [np.asarray(m, np.float32) for m in scene_flags.load_maps(
+        parser, args.predictions_directory, args.pred_suffix, frames)]
     results = consistency_flags.run(args, scene, frames, depth_maps, args.border)
     os.makedirs(args.output_directory, exist_ok=True)
     for frame, c, depth in zip(frames, results, depth_maps):

@@ -22,9 +22,7 @@ import sys
 
 import numpy as np
 
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
+from . import scene_flags
 
 
 def _floats(x):
@@ -41,14 +39,13 @@ def build_parser():
     p.add_argument("--schedule", choices=["resident", "reference"], default="resident",
                    help="raynet factory: per-ray columns resident in HBM (grouped by the free "
                         "memory) / the reference's literal recompute-everything schedule")
-    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
     p.add_argument("--filter_out", action="store_true", help="Filter out rays with zero ground-truth")
     # scripts/arguments.py:146-223 (generation)
-    p.add_argument("--patch_shape", type=_ints, default="11,11,3")
+    p.add_argument("--patch_shape", type=scene_flags.ints, default="11,11,3")
     p.add_argument("--padding", default=None, type=int)
     p.add_argument("--depth_planes", type=int, default=32)
     p.add_argument("--neighbors", type=int, default=4)
-    p.add_argument("--grid_shape", type=_ints, default="256,256,128")
+    p.add_argument("--grid_shape", type=scene_flags.ints, default="256,256,128")
     p.add_argument("--maximum_number_of_marched_voxels", type=int, default=650)
     p.add_argument("--sampling_policy",
                    choices=["sample_in_bbox", "sample_in_range", "sample_in_disparity"],
@@ -57,16 +54,11 @@ def build_parser():
                         "the voxel-space factories sample in the bounding box only)")
     p.add_argument("--depth_range", type=_floats, default="3.0,7.0",
                    help="The depth range used when sampling planes in range")
-    # :302-329 (dataset)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
-    # :335-358 (mrf, indexing)
+    # :302-329 (dataset) and :347-358 (indexing)
+    scene_flags.add_arguments(p)
+    # :335-345 (mrf)
     p.add_argument("--initial_gamma_prior", type=float, default=0.05)
     p.add_argument("--bp_iterations", type=int, default=3)
-    p.add_argument("--start_end", type=_ints, default="0,5")
-    p.add_argument("--skip_every", type=int, default=0)
     # :362-379 (forward pass factory)
     p.add_argument("--forward_pass_factory",
                    choices=["multi_view_cnn", "multi_view_cnn_voxel_space", "raynet"],
@@ -114,32 +106,23 @@ def main(argv=None):
         parser.error("--sampling_policy %s needs --forward_pass_factory multi_view_cnn: the "
                      "voxel-space factories (%s) march the voxels of the bounding-box segment"
                      % (args.sampling_policy, args.forward_pass_factory))
+    scene_flags.check(parser, args)
     import torch
     from raynet_amd.common.generation_parameters import GenerationParameters
-    from raynet_amd.common.scene import get_scene
     from raynet_amd.forward_pass import get_forward_pass_factory
 
     if not os.path.exists(args.output_directory):
         os.makedirs(args.output_directory)
     if isinstance(args.patch_shape, str):
-        args.patch_shape = _ints(args.patch_shape)
+        args.patch_shape = scene_flags.ints(args.patch_shape)
     if isinstance(args.grid_shape, str):
-        args.grid_shape = _ints(args.grid_shape)
-    if isinstance(args.start_end, str):
-        args.start_end = _ints(args.start_end)
+        args.grid_shape = scene_flags.ints(args.grid_shape)
     if isinstance(args.depth_range, str):
         args.depth_range = _floats(args.depth_range)
     args.grid_shape = np.array(args.grid_shape, dtype=np.int32)
     generation_params = GenerationParameters.from_options(args)
 
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-
+    scene = scene_flags.open_scene(args)
     model = load_model(args.weight_file, args.network_architecture,
                        in_channels=scene.get_image(0).image.shape[2])
 
@@ -151,6 +134,8 @@ def main(argv=None):
     fp = cls(model, generation_params, args.sampling_policy, scene.image_shape, args.rays_batch,
              **kwargs)
 
+    # (the range goes to the driver as given, not clamped to the scene as scene_flags.frames
+    # does: the driver walks it and the files are numbered by counting along)
     start, end = args.start_end
     ref_idx = start
     more = dict(with_statistics=True) if args.depth_statistics else {}

@@ -40,17 +40,11 @@ the mesh-cleanup flags
                      normals, colours and --mesh_cloud: see raynet_amd.scripts.mesh_flags
 """
 import argparse
-import os
 import sys
 
 import numpy as np
 
-from . import consistency_flags, mesh_flags, texture_flags
-from .convert_to_pointcloud import find_format
-
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
+from . import consistency_flags, mesh_flags, scene_flags, texture_flags
 
 
 def build_parser():
@@ -58,7 +52,7 @@ def build_parser():
     p.add_argument("dataset_directory", help="Directory containing the input data")
     p.add_argument("predictions_directory", help="Directory of the depth maps (depth_%%03d.npy)")
     p.add_argument("output_mesh", help="The PLY file to write the surface to")
-    p.add_argument("--grid_shape", type=_ints, default="256,256,128")
+    p.add_argument("--grid_shape", type=scene_flags.ints, default="256,256,128")
     p.add_argument("--truncation", type=float, default=None,
                    help="The truncation distance in scene units (default: 3 voxel sides)")
     p.add_argument("--min_weight", type=float, default=0.0,
@@ -77,33 +71,20 @@ def build_parser():
     p.add_argument("--normals", action="store_true", help="With vertex normals")
     p.add_argument("--color", action="store_true",
                    help="With vertex normals and the colours of the frames' images")
-    p.add_argument("--mesh_cloud", default=None,
-                   help="Also write --mesh_samples points of the surface as a point cloud (PLY) here")
-    p.add_argument("--mesh_samples", type=int, default=None,
-                   help="--mesh_cloud: how many area-weighted points to draw")
-    p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
+    mesh_flags.add_cloud_arguments(p)
     mesh_flags.add_arguments(p)
     texture_flags.add_arguments(p)
     consistency_flags.add_arguments(p)
-    # the dataset and indexing flags of raynet_amd.scripts.render_volume
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
-    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
-    p.add_argument("--start_end", type=_ints, default="0,5")
-    p.add_argument("--skip_every", type=int, default=0)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
+    scene_flags.add_arguments(p)
     return p
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    for name in ("start_end", "grid_shape"):
-        if isinstance(getattr(args, name), str):
-            setattr(args, name, _ints(getattr(args, name)))
-    if len(args.start_end) != 2:
-        parser.error("--start_end takes two numbers, START,END")
+    scene_flags.check(parser, args)
+    if isinstance(args.grid_shape, str):
+        args.grid_shape = scene_flags.ints(args.grid_shape)
     if len(args.grid_shape) != 3 or min(args.grid_shape) < 1:
         parser.error("--grid_shape takes three positive sizes, GX,GY,GZ")
     if args.truncation is not None and not 0.0 < args.truncation < float("inf"):
@@ -112,10 +93,7 @@ def main(argv=None):
         parser.error("--border takes a finite number of pixels, 0 or more")
     if not args.min_weight >= 0.0:
         parser.error("--min_weight takes a number that is 0 or more")
-    if args.mesh_cloud and args.mesh_samples is None:
-        parser.error("--mesh_cloud needs --mesh_samples N")
-    if args.mesh_samples is not None and (not args.mesh_cloud or args.mesh_samples < 1):
-        parser.error("--mesh_samples takes a positive number and goes with --mesh_cloud PATH")
+    mesh_flags.check_cloud(parser, args)
     if args.min_confidence is not None and not args.confidence_weights:
         parser.error("--min_confidence goes with --confidence_weights")
     if args.gt and args.confidence_weights:
@@ -125,41 +103,22 @@ def main(argv=None):
     consistency_flags.check(parser, args)
     if args.gt and consistency_flags.requested(args):
         parser.error("--min_consistent_views: ground-truth depth maps are not checked")
-    from raynet_amd.common.scene import get_scene
     from raynet_amd.fusion import fuse_scene
 
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    start, end = args.start_end
-    frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
-    if not frames:
-        parser.error("--start_end selects no frame of the scene")
-    if args.color and len(frames) > 32:
-        parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
-                     "--skip_every" % len(frames))
+    scene = scene_flags.open_scene(args)
+    frames = scene_flags.frames(parser, args, scene)
+    texture_flags.check_color_frames(parser, args, frames)
     texture_flags.check_frames(parser, args, frames)
     consistency_flags.check_frames(parser, args, frames)
     weights = None
     if args.gt:
         depth_maps = [scene.get_depth_map(i) for i in frames]
     else:
-        def load(key):
-            fmt = find_format(args.predictions_directory, key, frames[0])
-            files = [os.path.join(args.predictions_directory, fmt % (i,)) for i in frames]
-            missing = [f for f in files if not os.path.isfile(f)]
-            if missing:
-                parser.error("%d of %d %s maps are missing (first: %s)"
-                             % (len(missing), len(files), key, missing[0]))
-            return [np.load(f) for f in files]
-
-        depth_maps = load(args.pred_suffix)
+        depth_maps = scene_flags.load_maps(parser, args.predictions_directory, args.pred_suffix,
+                                           frames)
         if args.confidence_weights:
-            weights = [np.asarray(w, np.float32) for w in load("confidence")]
+            weights = [np.asarray(w, np.float32) for w in scene_flags.load_maps(
+                parser, args.predictions_directory, "confidence", frames)]
             if args.min_confidence is not None:
                 weights = [np.where(w >= np.float32(args.min_confidence), w, np.float32(0))
                            for w in weights]
@@ -175,12 +134,10 @@ def main(argv=None):
     if args.normals or args.color:
         mesh.compute_normals()
     if args.color:
-        mesh.colorize(scene, frames,
-                      tol=float(np.sqrt((mesh_flags.voxel_sides(volume) ** 2).sum())))
+        mesh.colorize(scene, frames, tol=mesh_flags.voxel_diagonal(volume))
     mesh.save_ply(args.output_mesh)
     if args.texture is not None:
-        texture_flags.write(parser, args, mesh, scene, frames,
-                            float(np.sqrt((mesh_flags.voxel_sides(volume) ** 2).sum())),
+        texture_flags.write(parser, args, mesh, scene, frames, mesh_flags.voxel_diagonal(volume),
                             args.output_mesh)
     if args.mesh_cloud:
         mesh.pointcloud(args.mesh_samples, args.seed).save_ply(args.mesh_cloud)

@@ -41,6 +41,9 @@
 --smooth_free_boundary       let the vertices on the mesh's border move too (default: pinned)
     (raynet_amd.smoothing).  Prints
     `smooth: N iterations, V vertices, farthest move M voxel sides`.
+
+--mesh_cloud PATH --mesh_samples N [--seed S]   also write N area-weighted points of the cleaned
+                             surface as a point cloud (add_cloud_arguments / check_cloud)
 """
 import math
 
@@ -88,6 +91,21 @@ def add_arguments(p):
     p.add_argument("--simplify_regularization", type=float, default=None,
                    help="--simplify_placement quadric: the pull back to the mean, in [2^-20, 1] "
                         "(2^-10)")
+
+
+def add_cloud_arguments(p):
+    p.add_argument("--mesh_cloud", default=None,
+                   help="Also write --mesh_samples points of the surface as a point cloud (PLY) here")
+    p.add_argument("--mesh_samples", type=int, default=None,
+                   help="--mesh_cloud: how many area-weighted points to draw")
+    p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
+
+
+def check_cloud(parser, args):
+    if args.mesh_cloud and args.mesh_samples is None:
+        parser.error("--mesh_cloud needs --mesh_samples N")
+    if args.mesh_samples is not None and (not args.mesh_cloud or args.mesh_samples < 1):
+        parser.error("--mesh_samples takes a positive number and goes with --mesh_cloud PATH")
 
 
 def given(args, flags=FLAGS):
@@ -153,6 +171,12 @@ def voxel_sides(volume):
     """The three sides of a voxel of the volume's grid, in scene units (float64)."""
     bbox = volume.bbox.astype(np.float64)
     return (bbox[3:] - bbox[:3]) / np.array(volume.grid_shape, np.float64)
+
+
+def voxel_diagonal(volume):
+    """The diagonal of a voxel of the volume's grid, in scene units: the slack of the occlusion
+    tests of --color and --texture."""
+    return float(np.sqrt((voxel_sides(volume) ** 2).sum()))
 
 
 def drop_components(mesh, args):

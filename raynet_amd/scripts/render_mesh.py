@@ -40,13 +40,9 @@ import sys
 
 import numpy as np
 
-from . import texture_flags
+from . import scene_flags, texture_flags
 
 PLANES = ("color", "normals", "shaded", "depth", "faces")
-
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
 
 
 def build_parser():
@@ -65,14 +61,7 @@ def build_parser():
     p.add_argument("--texture_tolerance", type=float, default=None,
                    help="--texture: the slack of the occlusion test in scene units (default: the "
                         "median edge length of the mesh)")
-    # the dataset and indexing flags of raynet_amd.scripts.forward_pass
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
-    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
-    p.add_argument("--start_end", type=_ints, default="0,5")
-    p.add_argument("--skip_every", type=int, default=0)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
+    scene_flags.add_arguments(p)
     return p
 
 
@@ -85,10 +74,7 @@ def _median_edge(mesh):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if isinstance(args.start_end, str):
-        args.start_end = _ints(args.start_end)
-    if len(args.start_end) != 2:
-        parser.error("--start_end takes two numbers, START,END")
+    scene_flags.check(parser, args)
     texture_flags.check(parser, args)
     if args.texture_tolerance is not None and args.texture is None:
         parser.error("--texture_tolerance goes with --texture T")
@@ -102,7 +88,7 @@ def main(argv=None):
             parser.error("--planes takes a comma-separated list of %s, got %r"
                          % (", ".join(PLANES), args.planes))
     try:
-        background = _ints(args.background)
+        background = scene_flags.ints(args.background)
     except ValueError:
         background = ()
     if len(background) != 3 or min(background) < 0 or max(background) > 255:
@@ -112,7 +98,6 @@ def main(argv=None):
     if not os.path.isfile(args.mesh_file):
         parser.error("%s: no such file (fuse_depth_maps and render_volume --mesh write one)"
                      % args.mesh_file)
-    from raynet_amd.common.scene import get_scene
     from raynet_amd.metrics import photometric_error
     from raynet_amd.volume import SurfaceMesh
 
@@ -126,17 +111,8 @@ def main(argv=None):
         parser.error("--compare scores the color renders: %s has no colours" % args.mesh_file)
     if mesh.empty:
         parser.error("%s: the mesh is empty, there is no surface to render" % args.mesh_file)
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    start, end = args.start_end
-    frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
-    if not frames:
-        parser.error("--start_end selects no frame of the scene")
+    scene = scene_flags.open_scene(args)
+    frames = scene_flags.frames(parser, args, scene)
     texture_flags.check_frames(parser, args, frames)
     if ("normals" in planes or "shaded" in planes) and mesh.normals is None:
         mesh.compute_normals()

@@ -42,13 +42,9 @@ import sys
 
 import numpy as np
 
-from . import mesh_flags, texture_flags
+from . import mesh_flags, scene_flags, texture_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
-
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
 
 
 def build_parser():
@@ -67,11 +63,7 @@ def build_parser():
                    help="Also write the surface at --threshold as a triangle mesh (PLY) here")
     p.add_argument("--open", action="store_true",
                    help="--mesh / --mesh_cloud: leave the surface open at the border of the grid")
-    p.add_argument("--mesh_cloud", default=None,
-                   help="Also write --mesh_samples points of the surface as a point cloud (PLY) here")
-    p.add_argument("--mesh_samples", type=int, default=None,
-                   help="--mesh_cloud: how many area-weighted points to draw")
-    p.add_argument("--seed", type=int, default=0, help="--mesh_cloud: the seed of the samples")
+    mesh_flags.add_cloud_arguments(p)
     p.add_argument("--color", action="store_true",
                    help="--mesh: with vertex normals and the colours of the frames' images")
     p.add_argument("--color_mode", choices=["blend", "best"], default="blend",
@@ -80,28 +72,15 @@ def build_parser():
                    help="--color: the slack of the occlusion test, in voxel diagonals")
     mesh_flags.add_arguments(p)
     texture_flags.add_arguments(p)
-    # the dataset and indexing flags of raynet_amd.scripts.forward_pass
-    p.add_argument("--dataset_type", choices=["restrepo", "dtu"], default="restrepo")
-    p.add_argument("--scene_idx", default=1, type=int, help="DTU: the scan number")
-    p.add_argument("--start_end", type=_ints, default="0,5")
-    p.add_argument("--skip_every", type=int, default=0)
-    p.add_argument("--select_neighbors_based_on", choices=["filesystem", "distance"],
-                   default="filesystem")
-    p.add_argument("--illumination_condition", default="max")
+    scene_flags.add_arguments(p)
     return p
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if isinstance(args.start_end, str):
-        args.start_end = _ints(args.start_end)
-    if len(args.start_end) != 2:
-        parser.error("--start_end takes two numbers, START,END")
-    if args.mesh_cloud and args.mesh_samples is None:
-        parser.error("--mesh_cloud needs --mesh_samples N")
-    if args.mesh_samples is not None and (not args.mesh_cloud or args.mesh_samples < 1):
-        parser.error("--mesh_samples takes a positive number and goes with --mesh_cloud PATH")
+    scene_flags.check(parser, args)
+    mesh_flags.check_cloud(parser, args)
     if (args.mesh or args.mesh_cloud) and not 0.0 < args.threshold <= 1.0:
         parser.error("--mesh / --mesh_cloud: --threshold must lie in (0, 1]")
     if args.color and not args.mesh:
@@ -113,23 +92,14 @@ def main(argv=None):
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
-    from raynet_amd.common.scene import get_scene
     from raynet_amd.volume import OccupancyVolume
 
     volume = OccupancyVolume.load(args.occupancy_file)
-    if args.dataset_type == "dtu":
-        scene = get_scene("dtu", args.dataset_directory, args.scene_idx,
-                          illumination=args.illumination_condition,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
-    else:
-        scene = get_scene("restrepo", args.dataset_directory,
-                          select_neighbors_based_on=args.select_neighbors_based_on)
+    scene = scene_flags.open_scene(args)
     os.makedirs(args.output_directory, exist_ok=True)
-    start, end = args.start_end
-    frames = list(range(start, min(end, scene.n_images), args.skip_every + 1))
-    if args.color and len(frames) > 32:
-        parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
-                     "--skip_every" % len(frames))
+    # (no frame is no error here: --ply and --mesh need none; --color says so itself, below)
+    frames = scene_flags.frames(parser, args, scene, required=False)
+    texture_flags.check_color_frames(parser, args, frames)
     texture_flags.check_frames(parser, args, frames)
     for i, r in zip(frames, volume.render_scene(scene, frames)):
         np.save(os.path.join(args.output_directory, "depth_%03d.npy" % (i,)),
@@ -139,19 +109,17 @@ def main(argv=None):
         volume.pointcloud(args.threshold, surface_only=not args.all_voxels).save_ply(args.ply)
     if args.mesh or args.mesh_cloud:
         mesh = mesh_flags.apply(volume.mesh(args.threshold, closed=not args.open), args, volume)
-        voxel = mesh_flags.voxel_sides(volume)
+        tol = args.depth_tolerance * mesh_flags.voxel_diagonal(volume)
         if args.mesh and args.color:
             if mesh.empty or not frames:
                 parser.error("--color: %s" % ("the surface is empty" if mesh.empty else
                                               "--start_end selects no frame of the scene"))
             mesh.compute_normals()
-            mesh.colorize(scene, frames, tol=args.depth_tolerance * float(np.sqrt((voxel ** 2).sum())),
-                          mode=args.color_mode)
+            mesh.colorize(scene, frames, tol=tol, mode=args.color_mode)
         if args.mesh:
             mesh.save_ply(args.mesh)
         if args.mesh and args.texture is not None:
-            texture_flags.write(parser, args, mesh, scene, frames,
-                                args.depth_tolerance * float(np.sqrt((voxel ** 2).sum())), args.mesh)
+            texture_flags.write(parser, args, mesh, scene, frames, tol, args.mesh)
         if args.mesh_cloud:
             if mesh.empty:
                 parser.error("no voxel reaches --threshold %g: the surface is empty and has no "

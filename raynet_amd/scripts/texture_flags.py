@@ -46,6 +46,13 @@ def check_frames(parser, args, frames):
                      "--skip_every" % (len(frames), MAX_FRAMES))
 
 
+def check_color_frames(parser, args, frames):
+    """--color blends the frames per vertex under the same limit."""
+    if args.color and len(frames) > MAX_FRAMES:
+        parser.error("--color: %d frames, at most 32 per mesh; choose them with --start_end / "
+                     "--skip_every" % len(frames))
+
+
 def bake(parser, args, mesh, scene, frames, tol):
     """-> texture.MeshTexture of the finished mesh from the frames, with --color's tolerance."""
     if mesh.empty or not frames:

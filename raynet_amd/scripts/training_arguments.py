@@ -4,9 +4,7 @@ import json
 
 import numpy as np
 
-
-def _ints(x):
-    return tuple(map(int, x.split(",")))
+from .scene_flags import ints as _ints
 
 
 def _floats(x):
