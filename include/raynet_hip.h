@@ -1048,6 +1048,65 @@ int rn_points_consistency(rn_ctx *ctx, int64_t n, const double *points, int32_t 
                           uint32_t *seen, uint32_t *agree, uint32_t *violate, float *residual,
                           void *stream);
 
+/* ---- which views to use: shared visibility, pair counts, covering sets ----
+ *
+ * rn_view_overlap: which of up to 64 views see every point, and how many points every pair of
+ * views shares at a useful triangulation angle.  All arrays are device memory.  points [3][n] f64,
+ * the coordinates as three rows; normals [3][n] f64 or NULL (no facing test); cameras [V][15] f64,
+ * a row P [3][4] row-major | centre [3] (as for rn_project_colors); depths [V][H][W] f32, distances
+ * to the camera centre, or NULL (no occlusion test).  1 <= V <= 64.  0 <= cos_lo <= cos_hi <= 1 are
+ * COSINES of the largest and the smallest triangulation angle that counts.
+ *
+ * Every operation is fp64 and rounded on its own, in the order written (the library is built with
+ * -ffp-contract=off); only + - * /, rint, comparisons and conversions occur -- no sqrt, no libm --
+ * and every count is an integer added by integer atomics, so the result is one fixed array
+ * whatever order the hardware ran the threads in, and a NumPy restatement gives the same integers
+ * (tests/view_selection_truth.py).
+ *
+ * View v sees point p = (x, y, z) with normal m -- exactly the per-view test of rn_project_colors,
+ * without the colour fetch:
+ *   projection   X, Y, d = c_v - p, dd = (d_x^2 + d_y^2) + d_z^2 and
+ *   in view      0 < h_2 < inf,  dd > 0,  border <= X <= (W - 1) - border,
+ *                border <= Y <= (H - 1) - border             (a NaN fails every test)
+ *   facing       with nn = (m_x^2 + m_y^2) + m_z^2 > 0 only:  dot = (m_x d_x + m_y d_y) + m_z d_z;
+ *                dot > 0  and  dot dot > (min_cos min_cos) (nn dd)
+ *   occlusion    with depths only:  zf = depths[v][rint(Y)][rint(X)] (half to even; a view that
+ *                does not count so far reads pixel (0, 0));  zf > 0  and  dd <= (zf + tol)^2
+ * Views i < j share p when both see it and, with a = c_i - p, b = c_j - p, dd_i, dd_j as above,
+ *   dot = (a_x b_x + a_y b_y) + a_z b_z;   q = dd_i dd_j;   dot2 = dot dot
+ *   dot > 0  and  dot2 >= lo2 q  and  dot2 <= hi2 q,   lo2 = cos_lo cos_lo,  hi2 = cos_hi cos_hi
+ * The band is decided on the squares as computed: with centres (0, 0, 4) and (3, 0, 4) and the
+ * point at the origin the cosine is 4/5 in exact arithmetic, but 0.8 * 0.8 * 400 rounds to
+ * 256.00000000000006 > 256 = dot2, and the pair does not count at cos_lo = 0.8.
+ *
+ * Written: visible [n] u64, bit v set iff view v sees point p, bits V and above 0 -- all n
+ * entries, always.  pairs [V][V] i64 is ADDED to: pairs[i][i] += the number of points view i sees,
+ * pairs[i][j] += the number of points i and j share for i < j; the lower triangle is never touched.
+ * The caller zeroes pairs; integer sums are free of order, so calls over the parts of a cloud add
+ * up to exactly the call over the whole.  A NaN or infinite point sets no bit.
+ *
+ * n == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch: n negative
+ * or above 2^38, V outside 1..64, H or W below 1, tol, min_cos or border negative or not finite,
+ * cos_lo, cos_hi not 0 <= cos_lo <= cos_hi <= 1, and with n > 0 a NULL points, cameras, visible or
+ * pairs. */
+int rn_view_overlap(rn_ctx *ctx, int64_t n, const double *points, const double *normals,
+                    int32_t V, const double *cameras, int32_t H, int32_t W, const float *depths,
+                    double tol, double min_cos, double border, double cos_lo, double cos_hi,
+                    uint64_t *visible, int64_t *pairs, void *stream);
+
+/* rn_view_gain: one round of a greedy covering set over rn_view_overlap's masks.  visible [n] u64
+ * and gain [V + 1] i64 are device memory; chosen is a 64-bit mask of the views taken so far, passed
+ * as a bit pattern (bit 63 is the sign bit).  A point is short when
+ *   popcount(visible[p] & chosen & (the low V bits)) < redundancy.
+ * gain is ADDED to: gain[v] += the number of short points with bit v set, for every v < V that is
+ * not in chosen (the entries of chosen views are not touched), and gain[V] += the number of short
+ * points.  The caller zeroes gain.  1 <= V <= 64, 1 <= redundancy <= 64.
+ *
+ * n == 0: RN_OK, no launch.  RN_ERR_INVALID, rn_last_error naming the entry, no launch: n negative
+ * or above 2^38, V or redundancy outside 1..64, and with n > 0 a NULL visible or gain. */
+int rn_view_gain(rn_ctx *ctx, int64_t n, const uint64_t *visible, int32_t V, int64_t chosen,
+                 int32_t redundancy, int64_t *gain, void *stream);
+
 /* ---- the connected components of an indexed triangle mesh ----
  *
  * rn_mesh_components: which piece every vertex belongs to, and how large the pieces are.  Two

@@ -213,6 +213,8 @@ SIGNATURES = {
     "rn_project_colors": [_P, _L, _P, _P, _I, _P, _I, _I, _I, _P, _P, _D, _D, _D, _I, _P, _P, _P, _P],
     "rn_tsdf_integrate": [_P, _I, _P, _I, _I, _P, _P, _D, _D, _P, _P, _P],
     "rn_points_consistency": [_P, _L, _P, _I, _P, _I, _I, _P, _I, _D, _D, _D, _P, _P, _P, _P, _P],
+    "rn_view_overlap": [_P, _L, _P, _P, _I, _P, _I, _I, _P, _D, _D, _D, _D, _D, _P, _P, _P],
+    "rn_view_gain": [_P, _L, _P, _I, _L, _I, _P, _P],
     "rn_mesh_components": [_P, _L, _L, _P, _P, _P, _P, _P, _P],
     "rn_mesh_smooth_workspace_bytes": [_P, _L, _L],
     "rn_mesh_smooth": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],

@@ -106,7 +106,28 @@ class Scene(object):
         path = os.path.join(basepath, dir)
         return [os.path.join(path, f) for f in sorted(filter(condition, os.listdir(path)))]
 
+    def use_overlap_neighbors(self, grid_shape=(32, 32, 32), min_angle=2.0, max_angle=45.0):
+        """From now on a frame's neighbours are the frames that share the most of the scene with
+        it: the centres of a coarse grid over the bbox stand in for the geometry, every camera of
+        the scene is asked which of them it sees (no normals, no depth maps), and two frames share
+        a centre both see at a triangulation angle within [min_angle, max_angle] degrees
+        (raynet_amd/view_selection.py; on the GPU, at most 64 images).  -> the ViewOverlap."""
+        from ..view_selection import MAX_VIEWS, view_overlap
+        n = int(self.n_images)
+        if n > MAX_VIEWS:
+            raise ValueError('%d images: neighbours by overlap take at most %d -- use '
+                             'select_neighbors_based_on="distance"' % (n, MAX_VIEWS))
+        centres = get_voxel_grid(self.bbox, grid_shape).reshape(3, -1).T
+        cameras = [self.get_image(k).camera for k in range(n)]
+        overlap = view_overlap(centres, cameras, self.image_shape, min_angle=min_angle,
+                               max_angle=max_angle)
+        self._overlap_neighbors = [overlap.neighbors(i, n - 1) for i in range(n)]
+        return overlap
+
     def _get_neighbor_idxs(self, i, neighbors):
+        table = getattr(self, "_overlap_neighbors", None)
+        if table is not None:
+            return [int(j) for j in table[int(i)][:neighbors]]
         if self._select_neighbors_based_on == "distance":
             if self._camera_neighbors is None:       # scene.py:59-79
                 a = np.hstack([self.get_image(k).camera.center for k in range(self.n_images)])

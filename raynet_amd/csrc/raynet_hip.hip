@@ -1244,6 +1244,10 @@ int rn_timer_stop(rn_ctx *ctx, void *stream, float *ms_out) {
 // what the other views say about a point: seen, agreeing and violated masks
 #include "raynet_consistency.inl"
 
+// which views see a point, the points every pair of views shares, a covering set's gains: ballots,
+// LDS counters and integer atomics
+#include "raynet_overlap.inl"
+
 // the connected components of a surface mesh: a lock-free union-find
 #include "raynet_components.inl"
 

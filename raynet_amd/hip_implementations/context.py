@@ -512,6 +512,71 @@ class HipContext(object):
             _ptr(outs[2]), _ptr(outs[3]), _stream()))
         return tuple(outs)
 
+    # ---- which views to use (raynet_amd/view_selection.py) -----------------------------------
+    def view_overlap(self, points, normals, cameras, image_shape, depths, tol, min_cos, border,
+                     cos_lo, cos_hi, visible=None, pairs=None):
+        """rn_view_overlap: points (3, n) f64, normals (3, n) f64 or None, cameras (V, 15) f64,
+        1 <= V <= 64, image_shape (H, W), depths (V, H, W) f32 or None, the band of the
+        triangulation angle as cosines 0 <= cos_lo <= cos_hi <= 1 -> (visible, pairs): [n] int64
+        (the bits of the u64 masks, bit v: view v sees the point) and (V, V) int64, which is ADDED
+        to -- the points every view sees on the diagonal, the points two views share above it; a
+        fresh one is zeroed here, a given one is the caller's."""
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[0] != 3:
+            raise ValueError("points: expected shape (3, n), got %s"
+                             % (tuple(getattr(points, "shape", ())),))
+        n = int(points.shape[1])
+        _chk(points, torch.float64, 3 * n, "points", align=8)
+        if normals is not None:
+            if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != (3, n):
+                raise ValueError("normals: expected shape (3, %d), got %s"
+                                 % (n, tuple(getattr(normals, "shape", ())),))
+            _chk(normals, torch.float64, 3 * n, "normals", align=8)
+        V = _table(cameras, 15, torch.float64, "cameras", align=8)
+        if not 1 <= V <= 64:
+            raise ValueError("cameras: 1 to 64 views (a bit of the mask each), got %d" % V)
+        H, W = (int(s) for s in image_shape)
+        if depths is not None and _stack(depths, V, "depths") != (V, H, W):
+            raise ValueError("depths: expected %s, got %s" % ((V, H, W), tuple(depths.shape)))
+        if visible is None:
+            visible = torch.empty((n,), dtype=torch.int64, device=points.device)
+        if pairs is None:
+            pairs = torch.zeros((V, V), dtype=torch.int64, device=points.device)
+        _chk(visible, torch.int64, n, "visible", align=8)
+        if tuple(pairs.shape) != (V, V):
+            raise ValueError("pairs: expected %s, got %s" % ((V, V), tuple(pairs.shape)))
+        _chk(pairs, torch.int64, V * V, "pairs", align=8)
+        self._check(self.lib.rn_view_overlap(
+            self._h, n, _ptr(points), _ptr(normals), V, _ptr(cameras), H, W, _ptr(depths),
+            float(tol), float(min_cos), float(border), float(cos_lo), float(cos_hi),
+            _ptr(visible), _ptr(pairs), _stream()))
+        return visible, pairs
+
+    def view_gain(self, visible, V, chosen, redundancy, gain=None):
+        """rn_view_gain: visible [n] int64 (the bits of rn_view_overlap's masks), V views, chosen:
+        the 64-bit mask of the views taken so far (a Python int, any 64 bits), redundancy 1..64 ->
+        gain [V + 1] int64, which is ADDED to (a fresh one is zeroed here): per view not in chosen
+        the number of points that fewer than `redundancy` chosen views see and that it sees; at V
+        the number of such points."""
+        V, redundancy = int(V), int(redundancy)
+        if not 1 <= V <= 64:
+            raise ValueError("V: 1 to 64 views, got %d" % V)
+        if not 1 <= redundancy <= 64:
+            raise ValueError("redundancy: 1 to 64, got %d" % redundancy)
+        if not isinstance(visible, torch.Tensor) or visible.dim() != 1:
+            raise ValueError("visible: expected shape (n,), got %s"
+                             % (tuple(getattr(visible, "shape", ())),))
+        n = int(visible.shape[0])
+        _chk(visible, torch.int64, n, "visible", align=8)
+        if gain is None:
+            gain = torch.zeros((V + 1,), dtype=torch.int64, device=visible.device)
+        _chk(gain, torch.int64, V + 1, "gain", align=8)
+        chosen = int(chosen) & 0xFFFFFFFFFFFFFFFF
+        if chosen >= 1 << 63:
+            chosen -= 1 << 64                   # the same 64 bits as an int64_t
+        self._check(self.lib.rn_view_gain(self._h, n, _ptr(visible), V, chosen, redundancy,
+                                          _ptr(gain), _stream()))
+        return gain
+
     # ---- connected components of a mesh (raynet_amd/components.py) ---------------------------
     def mesh_components(self, faces, n_vertices, labels=None, vertex_counts=None, face_counts=None):
         """rn_mesh_components: faces (nf, 3) i32 of a mesh with `n_vertices` vertices -> (labels,

@@ -56,6 +56,10 @@ def build_parser():
                    help="The depth range used when sampling planes in range")
     # :302-329 (dataset) and :347-358 (indexing)
     scene_flags.add_arguments(p)
+    p.add_argument("--neighbors_by_overlap", action="store_true",
+                   help="A frame's neighbours are the frames that share the most of the scene's "
+                        "bounding box with it at a useful triangulation angle (at most 64 images; "
+                        "raynet_amd.view_selection), not file order or camera distance")
     # :335-345 (mrf)
     p.add_argument("--initial_gamma_prior", type=float, default=0.05)
     p.add_argument("--bp_iterations", type=int, default=3)
@@ -107,6 +111,9 @@ def main(argv=None):
                      "voxel-space factories (%s) march the voxels of the bounding-box segment"
                      % (args.sampling_policy, args.forward_pass_factory))
     scene_flags.check(parser, args)
+    if args.neighbors_by_overlap and args.select_neighbors_based_on != "filesystem":
+        parser.error("--neighbors_by_overlap replaces --select_neighbors_based_on %s: give one of "
+                     "them" % args.select_neighbors_based_on)
     import torch
     from raynet_amd.common.generation_parameters import GenerationParameters
     from raynet_amd.forward_pass import get_forward_pass_factory
@@ -123,6 +130,11 @@ def main(argv=None):
     generation_params = GenerationParameters.from_options(args)
 
     scene = scene_flags.open_scene(args)
+    if args.neighbors_by_overlap:
+        try:
+            scene.use_overlap_neighbors()
+        except ValueError as e:             # (more than 64 images)
+            parser.error("--neighbors_by_overlap: %s" % e)
     model = load_model(args.weight_file, args.network_architecture,
                        in_channels=scene.get_image(0).image.shape[2])
 

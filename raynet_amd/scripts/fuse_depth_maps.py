@@ -30,6 +30,10 @@ observation ends.
 --volume OUT.npz     also save the volume (fusion.TSDFVolume.load reads it back)
 --normals, --color   the mesh file also carries vertex normals / the colours of the frames' images
                      (volume.SurfaceMesh.compute_normals / .colorize; at most 32 frames)
+--select_views K [--view_redundancy R]
+                     every frame (at most 64) is fused, but --color / --texture get only the
+                     K <= 32 frames that between them see the most of the finished surface
+                     (raynet_amd.scripts.view_flags); a line says which
 --mesh_cloud PATH --mesh_samples N [--seed S]
                      also write N area-weighted points of the surface as a point cloud, the form
                      compute_metrics scores
@@ -44,7 +48,7 @@ import sys
 
 import numpy as np
 
-from . import consistency_flags, mesh_flags, scene_flags, texture_flags
+from . import consistency_flags, mesh_flags, scene_flags, texture_flags, view_flags
 
 
 def build_parser():
@@ -74,6 +78,7 @@ def build_parser():
     mesh_flags.add_cloud_arguments(p)
     mesh_flags.add_arguments(p)
     texture_flags.add_arguments(p)
+    view_flags.add_arguments(p)
     consistency_flags.add_arguments(p)
     scene_flags.add_arguments(p)
     return p
@@ -100,6 +105,7 @@ def main(argv=None):
         parser.error("--confidence_weights: ground-truth depth maps have no confidence")
     mesh_flags.check(parser, args)
     texture_flags.check(parser, args)
+    view_flags.check(parser, args, used=bool(args.color or args.texture is not None))
     consistency_flags.check(parser, args)
     if args.gt and consistency_flags.requested(args):
         parser.error("--min_consistent_views: ground-truth depth maps are not checked")
@@ -107,8 +113,10 @@ def main(argv=None):
 
     scene = scene_flags.open_scene(args)
     frames = scene_flags.frames(parser, args, scene)
-    texture_flags.check_color_frames(parser, args, frames)
-    texture_flags.check_frames(parser, args, frames)
+    view_flags.check_candidates(parser, args, frames)
+    if not view_flags.requested(args):
+        texture_flags.check_color_frames(parser, args, frames)
+        texture_flags.check_frames(parser, args, frames)
     consistency_flags.check_frames(parser, args, frames)
     weights = None
     if args.gt:
@@ -133,12 +141,18 @@ def main(argv=None):
         parser.error("the fused surface is empty: no voxel pair straddles a measured depth")
     if args.normals or args.color:
         mesh.compute_normals()
+    color_frames = frames
+    if view_flags.requested(args):
+        color_frames = view_flags.choose(parser, args, mesh, scene, frames,
+                                         mesh_flags.voxel_diagonal(volume))
+        texture_flags.check_color_frames(parser, args, color_frames)
+        texture_flags.check_frames(parser, args, color_frames)
     if args.color:
-        mesh.colorize(scene, frames, tol=mesh_flags.voxel_diagonal(volume))
+        mesh.colorize(scene, color_frames, tol=mesh_flags.voxel_diagonal(volume))
     mesh.save_ply(args.output_mesh)
     if args.texture is not None:
-        texture_flags.write(parser, args, mesh, scene, frames, mesh_flags.voxel_diagonal(volume),
-                            args.output_mesh)
+        texture_flags.write(parser, args, mesh, scene, color_frames,
+                            mesh_flags.voxel_diagonal(volume), args.output_mesh)
     if args.mesh_cloud:
         mesh.pointcloud(args.mesh_samples, args.seed).save_ply(args.mesh_cloud)
     return 0

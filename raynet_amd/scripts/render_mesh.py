@@ -40,7 +40,7 @@ import sys
 
 import numpy as np
 
-from . import scene_flags, texture_flags
+from . import scene_flags, texture_flags, view_flags
 
 PLANES = ("color", "normals", "shaded", "depth", "faces")
 
@@ -58,6 +58,7 @@ def build_parser():
     p.add_argument("--compare", action="store_true",
                    help="Score the color renders against the frames' images")
     texture_flags.add_arguments(p, nearest=True)
+    view_flags.add_arguments(p)
     p.add_argument("--texture_tolerance", type=float, default=None,
                    help="--texture: the slack of the occlusion test in scene units (default: the "
                         "median edge length of the mesh)")
@@ -76,6 +77,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     scene_flags.check(parser, args)
     texture_flags.check(parser, args)
+    view_flags.check(parser, args, used=args.texture is not None)
     if args.texture_tolerance is not None and args.texture is None:
         parser.error("--texture_tolerance goes with --texture T")
     if args.texture_tolerance is not None and not 0.0 <= args.texture_tolerance < float("inf"):
@@ -113,7 +115,9 @@ def main(argv=None):
         parser.error("%s: the mesh is empty, there is no surface to render" % args.mesh_file)
     scene = scene_flags.open_scene(args)
     frames = scene_flags.frames(parser, args, scene)
-    texture_flags.check_frames(parser, args, frames)
+    view_flags.check_candidates(parser, args, frames)
+    if not view_flags.requested(args):
+        texture_flags.check_frames(parser, args, frames)
     if ("normals" in planes or "shaded" in planes) and mesh.normals is None:
         mesh.compute_normals()
     os.makedirs(args.output_directory, exist_ok=True)
@@ -127,7 +131,9 @@ def main(argv=None):
     textured = None
     if args.texture is not None:
         tol = _median_edge(mesh) if args.texture_tolerance is None else args.texture_tolerance
-        baked = texture_flags.bake(parser, args, mesh, scene, frames, tol)
+        texture_frames = view_flags.choose(parser, args, mesh, scene, frames, tol)
+        texture_flags.check_frames(parser, args, texture_frames)
+        baked = texture_flags.bake(parser, args, mesh, scene, texture_frames, tol)
         textured = rendered.textured(baked.with_unseen(), bilinear=not args.texture_nearest)
         baked.save_png(os.path.join(args.output_directory, "atlas.png"))
     scores, texture_scores = [], []

@@ -42,7 +42,7 @@ import sys
 
 import numpy as np
 
-from . import mesh_flags, scene_flags, texture_flags
+from . import mesh_flags, scene_flags, texture_flags, view_flags
 
 PLANES = ["depth", "expected_depth", "median_depth"]
 
@@ -72,6 +72,7 @@ def build_parser():
                    help="--color: the slack of the occlusion test, in voxel diagonals")
     mesh_flags.add_arguments(p)
     texture_flags.add_arguments(p)
+    view_flags.add_arguments(p)
     scene_flags.add_arguments(p)
     return p
 
@@ -89,6 +90,8 @@ def main(argv=None):
         parser.error("--depth_tolerance takes a finite number of voxel diagonals, 0 or more")
     mesh_flags.check(parser, args, mesh_requested=bool(args.mesh))
     texture_flags.check(parser, args, mesh_requested=bool(args.mesh))
+    view_flags.check(parser, args,
+                     used=bool(args.mesh) and (args.color or args.texture is not None))
     if not os.path.isfile(args.occupancy_file):
         parser.error("%s: no such file (forward_pass --save_occupancy writes it)"
                      % args.occupancy_file)
@@ -99,8 +102,10 @@ def main(argv=None):
     os.makedirs(args.output_directory, exist_ok=True)
     # (no frame is no error here: --ply and --mesh need none; --color says so itself, below)
     frames = scene_flags.frames(parser, args, scene, required=False)
-    texture_flags.check_color_frames(parser, args, frames)
-    texture_flags.check_frames(parser, args, frames)
+    view_flags.check_candidates(parser, args, frames)
+    if not view_flags.requested(args):
+        texture_flags.check_color_frames(parser, args, frames)
+        texture_flags.check_frames(parser, args, frames)
     for i, r in zip(frames, volume.render_scene(scene, frames)):
         np.save(os.path.join(args.output_directory, "depth_%03d.npy" % (i,)),
                 getattr(r, args.plane))
@@ -110,16 +115,21 @@ def main(argv=None):
     if args.mesh or args.mesh_cloud:
         mesh = mesh_flags.apply(volume.mesh(args.threshold, closed=not args.open), args, volume)
         tol = args.depth_tolerance * mesh_flags.voxel_diagonal(volume)
+        color_frames = frames
+        if args.mesh and view_flags.requested(args):
+            color_frames = view_flags.choose(parser, args, mesh, scene, frames, tol)
+            texture_flags.check_color_frames(parser, args, color_frames)
+            texture_flags.check_frames(parser, args, color_frames)
         if args.mesh and args.color:
-            if mesh.empty or not frames:
+            if mesh.empty or not color_frames:
                 parser.error("--color: %s" % ("the surface is empty" if mesh.empty else
                                               "--start_end selects no frame of the scene"))
             mesh.compute_normals()
-            mesh.colorize(scene, frames, tol=tol, mode=args.color_mode)
+            mesh.colorize(scene, color_frames, tol=tol, mode=args.color_mode)
         if args.mesh:
             mesh.save_ply(args.mesh)
         if args.mesh and args.texture is not None:
-            texture_flags.write(parser, args, mesh, scene, frames, tol, args.mesh)
+            texture_flags.write(parser, args, mesh, scene, color_frames, tol, args.mesh)
         if args.mesh_cloud:
             if mesh.empty:
                 parser.error("no voxel reaches --threshold %g: the surface is empty and has no "

@@ -228,6 +228,38 @@ class SurfaceMesh(object):
         self.colors = to_rgb8(got.colors, got.seen, unseen)
         return got.views
 
+    # ---- which frames to take colours from (view_selection.py) ---------
+    def best_frames(self, scene, frame_idxs, k, tol, min_cos=0.0, redundancy=1,
+                    return_stats=False):
+        """The (at most) k of the scene's frames `frame_idxs` (at most 64 candidates) that between
+        them see the most vertices, in the order a greedy covering set chooses them: every round
+        takes the frame that sees the most vertices fewer than `redundancy` chosen frames see yet,
+        the earlier of equals, until k are taken or no frame adds anything.  A frame sees a vertex
+        exactly as for `colorize`: it projects into the image, faces the frame (the vertex normal,
+        computed if absent, at cos > min_cos) and is no farther from the camera than the mesh's
+        own depth map there plus `tol`.  return_stats: -> (frames, gains, short), the vertices
+        every frame added and the number still short at the end."""
+        from .view_selection import MAX_VIEWS, view_overlap
+        frame_idxs = [int(i) for i in frame_idxs]
+        if self.empty:
+            raise ValueError("the mesh is empty: there is no surface to choose frames for")
+        if not 1 <= len(frame_idxs) <= MAX_VIEWS:
+            raise ValueError("%d candidate frames: 1 to %d per call" % (len(frame_idxs), MAX_VIEWS))
+        if int(k) < 0 or not 1 <= int(redundancy) <= MAX_VIEWS:
+            raise ValueError("k: 0 or more, redundancy: 1 to %d, got %r, %r"
+                             % (MAX_VIEWS, k, redundancy))
+        cameras = [scene.get_image(i).camera for i in frame_idxs]
+        H, W = scene.image_shape
+        caster = self.raycaster()
+        depth_maps = [caster.depth_map(cam, H, W) for cam in cameras]
+        if self.normals is None:
+            self.compute_normals()
+        overlap = view_overlap(self.vertices, cameras, (H, W), normals=self.normals,
+                               depth_maps=depth_maps, tol=tol, min_cos=min_cos)
+        order, gains, short = overlap.cover(k, redundancy)
+        chosen = [frame_idxs[v] for v in order]
+        return (chosen, gains, short) if return_stats else chosen
+
     # ---- a texture atlas (texture.py, DESIGN.md section 27) ---------------------------------
     def textured(self, scene, frame_idxs, T, tol, min_cos=0.0, mode="blend", normals="face"):
         """-> texture.MeshTexture: the images of the scene's frames `frame_idxs` (at most 32) baked
